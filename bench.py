@@ -8,6 +8,20 @@ Measures the BASELINE.json headline: train-step throughput (samples/sec,
 whole node) for GPT-2 under easydist_amd auto-SPMD, bf16 autocast,
 synthetic data, random-init weights; also reports the strategy-search
 wallclock. Weak scaling: per-GPU batch fixed, global batch = B * N.
+
+A plain run sets up, warms up, times --steps train steps and prints one
+JSON result line; that is everything the headline figure needs.
+  --dump-outputs DIR  after the timed steps, write what the last timed
+                      step computed as DIR/<name>.npy (float32): the loss
+                      the caller receives and a fixed, seeded sample of the
+                      parameters the step updated. Inputs and
+                      initial weights are seeded, so two builds run with the
+                      same arguments can be compared output for output.
+  --full              also run the secondary measurements and checks. The
+                      benchmark has none of its own today (the comparison
+                      harnesses live in benchmark/), so the flag changes
+                      nothing yet; anything added later that the headline
+                      figure does not need goes behind it.
 """
 from __future__ import annotations
 
@@ -38,7 +52,41 @@ def _comm_summary(compiled):
         return None
 
 
-def main():
+# --dump-outputs: elements sampled per parameter tensor (GPT-2 small has
+# 149 of them -> ~2.4 MB of float32); the whole sample stays under 64 MB
+_DUMP_PER_PARAM = 4096
+_DUMP_MAX_ELEMS = 15 * 1024 * 1024
+_DUMP_SEED = 20240
+
+
+def _dump_outputs(out_dir, loss, compiled, rank):
+    """Write the last timed step's results as float32 .npy files."""
+    import numpy as np
+    # the compiled step keeps the trained parameters in its own state;
+    # compiled.named_parameters() is how a caller reads them back (it
+    # gathers shards, so every rank takes part and rank 0 writes)
+    named = compiled.named_parameters()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().to(torch.float32).cpu().numpy())
+    # the same seeded positions are sampled in every run
+    g = torch.Generator(device="cpu").manual_seed(_DUMP_SEED)
+    per_param = max(1, min(_DUMP_PER_PARAM,
+                           _DUMP_MAX_ELEMS // max(len(named), 1)))
+    parts = []
+    for prm in named.values():
+        flat = prm.detach().reshape(-1)
+        if flat.numel() > per_param:
+            pos = torch.randint(0, flat.numel(), (per_param,), generator=g)
+            flat = flat[pos.to(flat.device)]
+        parts.append(flat.to(torch.float32).cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            torch.cat(parts).numpy())
+
+
+def _parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
@@ -55,7 +103,18 @@ def main():
     # capture falls back to the decomposed per-param math
     p.add_argument("--hipgraph", action="store_true")
     p.add_argument("--no-hipgraph", action="store_true")   # back-compat
-    args = p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/*.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run secondary measurements (none today)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = _parse_args()
 
     import torch.distributed as dist
 
@@ -174,6 +233,9 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1000.0
     samples_per_sec = global_batch * args.steps / elapsed
+
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, loss, compiled, rank)
 
     if rank == 0:
         family = ("vit" if args.model.startswith("vit")

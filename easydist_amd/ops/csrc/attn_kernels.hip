@@ -592,8 +592,11 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
       const int e = threadIdx.x * 8 + pi * 4096;
-      kreg[pi] = *reinterpret_cast<const bf16x8*>(&k[(long)t0 * D + e]);
-      vreg[pi] = *reinterpret_cast<const bf16x8*>(&v[(long)t0 * D + e]);
+      // row strides: the inputs may be [B,S,H,D]-layout views
+      const long row = t0 + e / D;
+      const int col = e % D;
+      kreg[pi] = *reinterpret_cast<const bf16x8*>(&k[row * kss + col]);
+      vreg[pi] = *reinterpret_cast<const bf16x8*>(&v[row * vss + col]);
     }
   };
   auto kv_store = [&](int buf) {
@@ -795,8 +798,11 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
       const int e = threadIdx.x * 8 + pi * 4096;
-      qreg[pi] = *reinterpret_cast<const bf16x8*>(&q[(long)t0 * D + e]);
-      dreg[pi] = *reinterpret_cast<const bf16x8*>(&dO_[(long)t0 * D + e]);
+      // row strides: the inputs may be [B,S,H,D]-layout views
+      const long row = t0 + e / D;
+      const int col = e % D;
+      qreg[pi] = *reinterpret_cast<const bf16x8*>(&q[row * qss + col]);
+      dreg[pi] = *reinterpret_cast<const bf16x8*>(&dO_[row * dss + col]);
     }
   };
   auto q_store = [&](int buf) {

@@ -181,6 +181,44 @@ def test_flash_attn_bwd(ext):
 
 
 @requires_gpu
+def test_flash_attn_bwd_strided_views(ext):
+    # the model feeds [B,S,H,D]-layout views: q/k/v split out of one qkv
+    # projection (row stride 3*H*D) and a transposed grad (row stride H*D).
+    # Same data, same arithmetic -> bit-equal to the contiguous call, and
+    # within the contiguous test's bound of the fp32 reference.
+    torch.manual_seed(11)
+    for (B, H, S, D) in [(2, 3, 256, 64), (1, 2, 256, 128)]:
+        qkv = torch.randn(B, S, 3 * H * D, device="cuda",
+                          dtype=torch.bfloat16)
+        q, k, v = (t.view(B, S, H, D).transpose(1, 2)
+                   for t in qkv.split(H * D, dim=2))
+        g = torch.randn(B, S, H * D, device="cuda", dtype=torch.bfloat16) \
+            .view(B, S, H, D).transpose(1, 2)
+        assert not q.is_contiguous() and not g.is_contiguous()
+        qc, kc, vc, gc = (t.contiguous() for t in (q, k, v, g))
+        out, lse = ext.flash_attn_fwd(qc, kc, vc, True)
+        want = ext.flash_attn_bwd(gc, qc, kc, vc, out, lse, True)
+        got = ext.flash_attn_bwd(g, q, k, v, out, lse, True)
+        for a, b, name in zip(got, want, ("dq", "dk", "dv")):
+            assert torch.equal(a, b), \
+                (name, float((a.float() - b.float()).abs().max()), B, H, S, D)
+        packed = ext.flash_attn_bwd_pack(g, q, k, v, out, lse, True)
+        ref_packed = torch.cat([d.transpose(1, 2).reshape(B, S, H * D)
+                                for d in want], -1)
+        assert torch.equal(packed, ref_packed)
+        qf = qc.float().requires_grad_(True)
+        kf = kc.float().requires_grad_(True)
+        vf = vc.float().requires_grad_(True)
+        ref = torch.nn.functional.scaled_dot_product_attention(
+            qf, kf, vf, is_causal=True)
+        ref.backward(gc.float())
+        for a, w, name in zip(got, (qf.grad, kf.grad, vf.grad),
+                              ("dq", "dk", "dv")):
+            err = (a.float() - w).abs().max()
+            assert err < 8e-2, (name, float(err), B, H, S, D)
+
+
+@requires_gpu
 def test_gemm_nt_256_path(ext):
     # clean 256x256-tile shapes plus M/N tails (row-clamped staging)
     torch.manual_seed(5)
