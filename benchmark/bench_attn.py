@@ -1,7 +1,22 @@
 #!/usr/bin/env python3
-"""Flash attention kernel timing on the GPT-2 bench shape."""
+"""Flash attention kernel timing: fwd, dq and dkv, causal and not, under
+both workgroup maps (EASYDIST_ATTN_MAP, read by the launch code at every
+call so one process can alternate them).
+
+Event timings give fwd and total bwd (delta + dq + dkv).  Per-kernel
+figures for dq and dkv come from a kernel trace: either run this script
+under `rocprofv3 --kernel-trace --stats` with one --map and one --causal
+value, in a run of its own, or pass --per-kernel to collect them with the
+torch profiler in-process (attributed per configuration).
+
+Every configuration is timed --repeats times, the maps alternated inside
+each repeat, and min / median / max are reported so a difference can be
+set against the run-to-run spread.  One JSON line per configuration.
+"""
+import argparse
 import json
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
@@ -9,6 +24,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import torch
 
 import easydist_amd.ops as ops
+
+SHAPES = [(64, 12, 1024, 64), (16, 16, 2048, 128),
+          (64, 12, 1152, 64)]   # nblk = 9: legacy map is naturally mixed
+
+# report name -> substring of the kernel's name in a trace
+KERNELS = {"fwd": "flash_fwd", "dq": "flash_bwd_dq", "dkv": "flash_bwd_dkv",
+           "delta": "attn_delta"}
 
 
 def time_ms(fn, iters=10, warmup=3):
@@ -24,26 +46,109 @@ def time_ms(fn, iters=10, warmup=3):
     return s.elapsed_time(e) / iters
 
 
+def kernel_ms(fn, iters):
+    """Mean device time per call of each flash kernel, via the profiler."""
+    acts = [torch.profiler.ProfilerActivity.CPU,
+            torch.profiler.ProfilerActivity.CUDA]
+    fn()
+    torch.cuda.synchronize()
+    with torch.profiler.profile(activities=acts) as prof:
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+    out = {}
+    for ev in prof.key_averages():
+        for tag in KERNELS.values():
+            if tag in ev.key:
+                us = getattr(ev, "device_time_total", None)
+                if us is None:
+                    us = ev.cuda_time_total
+                if us:
+                    out[tag] = out.get(tag, 0.0) + us / 1e3 / iters
+    return out
+
+
+def stats(xs):
+    return {"min": min(xs), "med": statistics.median(xs), "max": max(xs),
+            "all": [round(x, 4) for x in xs]}   # in measurement order
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--causal", choices=["0", "1", "both"], default="1")
+    ap.add_argument("--map", choices=["0", "1", "both", "env"], default="env",
+                    help="workgroup map: 0 legacy, 1 balanced, both = "
+                         "alternate them, env = leave EASYDIST_ATTN_MAP alone")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warm-iters", type=int, default=50)
+    ap.add_argument("--shapes", default="all",
+                    help="comma-separated indices into the shape list")
+    ap.add_argument("--per-kernel", action="store_true",
+                    help="also report per-kernel device time (torch profiler)")
+    args = ap.parse_args()
+
     ext = ops.load_extension()
     assert ext is not None
-    out = []
-    for (B, H, S, D) in [(64, 12, 1024, 64), (16, 16, 2048, 128)]:
+    causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
+    maps = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}[args.map]
+    shapes = SHAPES if args.shapes == "all" else \
+        [SHAPES[int(i)] for i in args.shapes.split(",")]
+
+    def set_map(m):
+        if m is not None:
+            os.environ["EASYDIST_ATTN_MAP"] = m
+
+    for (B, H, S, D) in shapes:
         q = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16)
         k = torch.randn_like(q)
         v = torch.randn_like(q)
-        o, lse = ext.flash_attn_fwd(q, k, v, True)
-        g = torch.randn_like(o)
-        t_fwd = time_ms(lambda: ext.flash_attn_fwd(q, k, v, True))
-        t_bwd = time_ms(lambda: ext.flash_attn_bwd(g, q, k, v, o, lse, True))
-        # causal flops
-        fl_fwd = 2.0 * B * H * S * S * D * 2 / 2
-        fl_bwd = fl_fwd * 2.5
-        r = {"shape": f"B{B} H{H} S{S} D{D}", "fwd_ms": t_fwd,
-             "bwd_ms": t_bwd, "fwd_tf": fl_fwd / t_fwd / 1e9,
-             "bwd_tf": fl_bwd / t_bwd / 1e9}
-        out.append(r)
-        print(json.dumps(r))
+        g = torch.randn_like(q)
+        for causal in causals:
+            o, lse = ext.flash_attn_fwd(q, k, v, causal)
+            fwd = lambda: ext.flash_attn_fwd(q, k, v, causal)
+            bwd = lambda: ext.flash_attn_bwd(g, q, k, v, o, lse, causal)
+            t_fwd = {m: [] for m in maps}
+            t_bwd = {m: [] for m in maps}
+            t_k = {m: {n: [] for n in KERNELS} for m in maps}
+            # bring clocks and caches to steady state before the first
+            # repeat: without this the first repeat of a configuration
+            # reads ~10% high and sets the whole min-max spread
+            for m in maps:
+                set_map(m)
+                time_ms(fwd, args.warm_iters, 0)
+                time_ms(bwd, args.warm_iters, 0)
+            for _ in range(args.repeats):
+                for m in maps:          # alternate maps inside a repeat
+                    set_map(m)
+                    t_fwd[m].append(time_ms(fwd, args.iters))
+                    t_bwd[m].append(time_ms(bwd, args.iters))
+                    if args.per_kernel:
+                        km = kernel_ms(fwd, args.iters)
+                        km.update(kernel_ms(bwd, args.iters))
+                        for n, tag in KERNELS.items():
+                            if tag in km:
+                                t_k[m][n].append(km[tag])
+            # matmul flops the fwd does: QK^T + PV, halved under the mask
+            fl_fwd = 2.0 * B * H * S * S * D * 2 * (0.5 if causal else 1.0)
+            fl_bwd = fl_fwd * 2.5       # model flops of the backward
+            for m in maps:
+                r = {"shape": f"B{B} H{H} S{S} D{D}", "causal": int(causal),
+                     "map": m if m is not None
+                     else os.environ.get("EASYDIST_ATTN_MAP", "1"),
+                     "fwd_ms": stats(t_fwd[m]), "bwd_ms": stats(t_bwd[m])}
+                r["fwd_tf"] = fl_fwd / r["fwd_ms"]["med"] / 1e9
+                r["bwd_tf"] = fl_bwd / r["bwd_ms"]["med"] / 1e9
+                if args.per_kernel:
+                    r["kernel_ms"] = {n: stats(xs)
+                                      for n, xs in t_k[m].items() if xs}
+                    # executed matmuls: fwd 2, dq 3 (S, dP, dQ), dkv 4
+                    # (S^T, dV, dP^T, dK) -> 1.5x and 2x the fwd flops
+                    r["kernel_tf"] = {
+                        n: fl_fwd * f / r["kernel_ms"][n]["med"] / 1e9
+                        for n, f in (("fwd", 1.0), ("dq", 1.5), ("dkv", 2.0))
+                        if n in r["kernel_ms"]}
+                print(json.dumps(r), flush=True)
 
 
 if __name__ == "__main__":

@@ -9,8 +9,10 @@
 // fragment group. P round-trips through a wave-private LDS strip to
 // re-fragment from the S layout to the PV A-operand layout.
 #include "common.h"
+#include "attn_block_map.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <climits>
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using bf16x8v = __attribute__((ext_vector_type(8))) __bf16;
@@ -90,8 +92,9 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                  float* __restrict__ LSE, int B, int H, int S, bool causal,
                  float scale,
                  long qsb, long qsh, long qss, long ksb, long ksh, long kss,
-                 long vsb, long vsh, long vss) {
-  // grid: (ceil(S/QBLK), B*H); QBLK = 128*RF q rows per workgroup, 8
+                 long vsb, long vsh, long vss, int map_mode) {
+  // grid: 1-D, ceil(S/QBLK) * B*H workgroups placed by attn_block_map
+  // (attn_block_map.h); QBLK = 128*RF q rows per workgroup, 8
   // waves of RF 16-row fragments each.  The round-1 4-wave/256-thread
   // form ran ONE wave per SIMD (110 KB LDS) — every softmax/LDS stall
   // fully exposed, ~100 TF effective.  8 waves + the smaller strip pool
@@ -99,8 +102,10 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
   // each staged K/V tile (half the staging + barrier cost per flop) at
   // one wave/SIMD lower occupancy — A/B'd on hardware.
   constexpr int QBLK = 8 * 16 * RF;
-  const int qb0 = blockIdx.x * QBLK;
-  const int bh = blockIdx.y;
+  const AttnBlock wgm = attn_block_map(blockIdx.x, (S + QBLK - 1) / QBLK,
+                                       B * H, causal, map_mode);
+  const int qb0 = wgm.blk * QBLK;
+  const int bh = wgm.bh;
   const int b_ = bh / H, h_ = bh % H;
   // inputs may be [B,S,H,D]-layout views (the qkv split) — per-tensor
   // batch/head/row strides avoid the activation-sized .contiguous()
@@ -452,6 +457,21 @@ static inline at::Tensor ed_attn_arg(const at::Tensor& t) {
   return t.stride(3) == 1 ? t : t.contiguous();
 }
 
+// EASYDIST_ATTN_MAP: 1 = balanced (default), 0 = legacy placement, kept
+// for A/B timing.  Read at every launch, not cached in a static, so one
+// process can run both maps; a getenv is nothing next to these kernels.
+static inline int ed_attn_map_mode() {
+  const char* e = getenv("EASYDIST_ATTN_MAP");
+  return (e && atoi(e) == 0) ? ATTN_MAP_LEGACY : ATTN_MAP_BALANCED;
+}
+
+// 1-D grid of nblk * nbh workgroups: the linear id the map consumes
+static inline dim3 ed_attn_grid(long nblk, long nbh, const char* who) {
+  TORCH_CHECK(nblk * nbh <= (long)INT_MAX, who,
+              ": workgroup count ", nblk * nbh, " does not fit in an int");
+  return dim3((unsigned)(nblk * nbh));
+}
+
 std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
                                                   const at::Tensor& k_,
                                                   const at::Tensor& v_,
@@ -479,7 +499,9 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
     return e ? atoi(e) : 1;
   }();
   const int use_rf = (rf == 2 && S % 256 == 0) ? 2 : 1;
-  dim3 grid((S + 128 * use_rf - 1) / (128 * use_rf), B * H), block(512);
+  dim3 grid = ed_attn_grid((S + 128 * use_rf - 1) / (128 * use_rf),
+                           (long)B * H, "flash_attn_fwd"), block(512);
+  const int map_mode = ed_attn_map_mode();
   size_t lds = (2 * ((size_t)KB * D + (size_t)KB * D) + 8 * 16 * KB) * 2;
   float scale = 1.f / sqrtf((float)D);
   auto kern = (D == 64)
@@ -495,7 +517,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
       lse.data_ptr<float>(), B, H, S, causal, scale,
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2));
+      v.stride(0), v.stride(1), v.stride(2), map_mode);
   return {out, lse};
 }
 
@@ -521,11 +543,15 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     int B, int H, int S, bool causal, float scale,
                     long dsb, long dsh, long dss, long qsb, long qsh,
                     long qss, long ksb, long ksh, long kss, long vsb,
-                    long vsh, long vss, long osb, long osh, long oss) {
+                    long vsh, long vss, long osb, long osh, long oss,
+                    int map_mode) {
   // 8 waves x 16 q rows: two 64-row halves share each staged K/V tile
   // (2x arithmetic intensity vs the 4-wave form) at 6+ waves/SIMD.
-  const int qb0 = blockIdx.x * (2 * QB);
-  const int bh = blockIdx.y;
+  // grid: 1-D, S/128 * B*H workgroups placed by attn_block_map
+  const AttnBlock wgm = attn_block_map(blockIdx.x, S / (2 * QB), B * H,
+                                       causal, map_mode);
+  const int qb0 = wgm.blk * (2 * QB);
+  const int bh = wgm.bh;
   const int b_ = bh / H, h_ = bh % H;
   const bf16* dO_ = dO + b_ * dsb + h_ * dsh;
   const bf16* q = Q + b_ * qsb + h_ * qsh;
@@ -745,10 +771,15 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      float scale,
                      long dsb, long dsh, long dss, long qsb, long qsh,
                      long qss, long ksb, long ksh, long kss, long vsb,
-                     long vsh, long vss, long osb, long osh, long oss) {
+                     long vsh, long vss, long osb, long osh, long oss,
+                     int map_mode) {
   // 8 waves x 16 key rows share each staged Q/dO tile (see dq note)
-  const int kb0 = blockIdx.x * (2 * KB);
-  const int bh = blockIdx.y;
+  // grid: 1-D as in dq; kv block 0 is the causal-heavy one here, so the
+  // map keeps the index order (heavy_last_index = false)
+  const AttnBlock wgm = attn_block_map(blockIdx.x, S / (2 * KB), B * H,
+                                       false, map_mode);
+  const int kb0 = wgm.blk * (2 * KB);
+  const int bh = wgm.bh;
   const int b_ = bh / H, h_ = bh % H;
   const bf16* dO_ = dO + b_ * dsb + h_ * dsh;
   const bf16* q = Q + b_ * qsb + h_ * qsh;
@@ -1056,7 +1087,9 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
         grad.stride(0), grad.stride(1), grad.stride(2));
   }
   auto stream = at::cuda::getCurrentCUDAStream();
-  dim3 grid(S / (2 * QB), B * H), block(512);
+  dim3 grid = ed_attn_grid(S / (2 * QB), (long)B * H, "flash_attn_bwd"),
+       block(512);
+  const int map_mode = ed_attn_map_mode();
   // dq: DOUBLE-buffered (K+V+K^T) tiles + wave strips
   size_t lds = (2 * (3 * (size_t)KB * D) + 8 * 16 * KB) * 2;
   // dkv: DOUBLE-buffered (Q+dO+Q^T+dO^T) tiles + wave strips
@@ -1084,7 +1117,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       grad.stride(0), grad.stride(1), grad.stride(2),
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss);
+      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode);
   hipLaunchKernelGGL(kkern, grid, block, lds_kv, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
@@ -1093,7 +1126,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       grad.stride(0), grad.stride(1), grad.stride(2),
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss);
+      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor>

@@ -26,6 +26,7 @@
 //   D[m][n] += sum_k A[m][k]*B[n][k]; A/B: lane holds row (l&15),
 //   k = (l>>4)*8..+8; C/D: lane holds col (l&15), rows (l>>4)*4+r.
 #include "common.h"
+#include "attn_block_map.h"   // xcd_swizzle, N_XCD
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -33,15 +34,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using bf16x8v = __attribute__((ext_vector_type(8))) __bf16;
 using v4s = __attribute__((ext_vector_type(4))) short;
 using v8s = __attribute__((ext_vector_type(8))) short;
-
-#define N_XCD 8
-
-// bijective XCD-aware workgroup remap (cdna_hip_programming.md T1)
-DEVINL unsigned xcd_swizzle(unsigned wg, unsigned nwg) {
-  unsigned q = nwg / N_XCD, r = nwg % N_XCD;
-  unsigned xcd = wg % N_XCD, idx = wg / N_XCD;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 // global_load_lds: LDS dest is wave-uniform base + lane*16
 DEVINL void glds16(const void* gsrc, void* lds_dst) {
