@@ -27,6 +27,7 @@
 //   k = (l>>4)*8..+8; C/D: lane holds col (l&15), rows (l>>4)*4+r.
 #include "common.h"
 #include "attn_block_map.h"   // xcd_swizzle, N_XCD
+#include "gemm_tn_map.h"      // gemm_tn_map: wg id -> (tile, slice)
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -544,15 +545,15 @@ DEVINL bf16x8v tn_frag(const char* img, int chunk, int lane) {
 extern "C" __global__ void __launch_bounds__(256)
 gemm_tn_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
                float* __restrict__ Cw, float* __restrict__ Asum,
-               int R, int P, int Q, int splitr) {
+               int R, int P, int Q, int splitr, int map_mode) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned IMG = TBR * TBP * 2;          // 8 KiB per operand image
   const unsigned BUF = 2 * IMG;                // A+B per buffer
 
   unsigned nwg_p = P / TBP, nwg_q = Q / TBP;
   unsigned ntile = nwg_p * nwg_q;
-  unsigned wg = xcd_swizzle(blockIdx.x, ntile * splitr);
-  unsigned tile = wg / splitr, slice = wg % splitr;
+  const TnBlock blk = gemm_tn_map(blockIdx.x, ntile, splitr, map_mode);
+  const unsigned tile = blk.tile, slice = blk.slice;
   const unsigned p0 = (tile / nwg_q) * TBP;
   const unsigned q0 = (tile % nwg_q) * TBP;
 
@@ -657,11 +658,16 @@ gemm_tn_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
 // gemm_tn_256: 256x256 output tile, 512 threads (8 waves of 64x128).
 // Same tr-read image scheme as gemm_tn_kernel but with DOUBLE the tile
 // edge: operand re-read traffic scales with 1/tile_edge (A is re-read
-// Q/tile times, B P/tile times), and the 128x128 kernel measures exactly
-// at that memory floor (3.6 GB -> 0.57 ms on the 65536-row dW shapes).
-// The square 256 tile halves it. Occupancy is VGPR-bound at 2 waves/SIMD
-// (acc[4][8] = 128 VGPRs) -- acceptable: the loop is HBM-bound, the
-// double-buffered glds prefetch covers what latency can be covered.
+// Q/tile times, B P/tile times).  Occupancy is VGPR-bound at 2 waves/SIMD
+// (acc[4][8] = 128 VGPRs), one workgroup per CU.
+//
+// What bounds the r-loop (measured, profiles/README.md Round 4): NOT HBM.
+// At the 65536-row dW shapes the old issue-then-drain loop pulled 3-4 TB/s
+// from beyond the L2 with the MFMA pipe ~40% busy; it sat on the loaded
+// latency of the ONE 32 KiB stage it kept in flight and drained before
+// every barrier.  Moving the operand re-reads into the L2 (slice-major
+// map, gemm_tn_map.h: beyond-L2 bytes -54..-62%) bought only 1-6%; keeping
+// two stages in flight (three-buffer ring below) bought 7-24%.
 // ===========================================================================
 #define TBP2 256
 
@@ -685,10 +691,17 @@ DEVINL void tn_stage2(const bf16* src, long ld, int r0, int p0, int pmax,
   }
 }
 
-extern "C" __global__ void __launch_bounds__(512)
-gemm_tn_256_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
-                   float* __restrict__ Cw, float* __restrict__ Asum,
-                   int R, int P, int Q, int splitr) {
+// RING selects the r-loop's staging:
+//   1  three 32-row buffers, two stages in flight: counted vmcnt(4) (a
+//      stage is 4 glds per thread) and a raw barrier -- never
+//      __syncthreads, whose fence would drain the stage in flight (96 KiB)
+//   0  the old loop, kept for A/B: two buffers, stage rt+1, compute rt,
+//      drain, barrier (64 KiB)
+template <int RING>
+DEVINL void tn256_body(const bf16* __restrict__ Ag,
+                       const bf16* __restrict__ Bg, float* __restrict__ Cw,
+                       float* __restrict__ Asum, int R, int P, int Q,
+                       int splitr, int map_mode) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned IMG = TBR * TBP2 * 2;         // 16 KiB per operand image
   const unsigned BUF = 2 * IMG;                // A+B per buffer
@@ -697,8 +710,8 @@ gemm_tn_256_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
   // row to pmax-1 (duplicate loads) and the store loop guards gp/gq
   unsigned nwg_p = (P + TBP2 - 1) / TBP2, nwg_q = (Q + TBP2 - 1) / TBP2;
   unsigned ntile = nwg_p * nwg_q;
-  unsigned wg = xcd_swizzle(blockIdx.x, ntile * splitr);
-  unsigned tile = wg / splitr, slice = wg % splitr;
+  const TnBlock blk = gemm_tn_map(blockIdx.x, ntile, splitr, map_mode);
+  const unsigned tile = blk.tile, slice = blk.slice;
   const unsigned p0 = (tile / nwg_q) * TBP2;
   const unsigned q0 = (tile % nwg_q) * TBP2;
 
@@ -714,9 +727,13 @@ gemm_tn_256_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
   const int wp = (wave >> 1) * 64;             // 4 p-rows of waves
   const int wq = (wave & 1) * 128;             // 2 q-cols of waves
 
+  // r-tile rt into buffer buf (past rt1: skipped, uniformly over the
+  // workgroup)
   auto stage = [&](int buf, int rt) {
-    tn_stage2(Ag, P, rt * TBR, p0, P, smem + buf * BUF, t, wave);
-    tn_stage2(Bg, Q, rt * TBR, q0, Q, smem + buf * BUF + IMG, t, wave);
+    if (rt < rt1) {
+      tn_stage2(Ag, P, rt * TBR, p0, P, smem + buf * BUF, t, wave);
+      tn_stage2(Bg, Q, rt * TBR, q0, Q, smem + buf * BUF + IMG, t, wave);
+    }
   };
 
   f32x4 acc[4][8];
@@ -727,16 +744,12 @@ gemm_tn_256_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
     for (int j = 0; j < 8; ++j)
       acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  stage(0, rt0);
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  for (int rt = rt0; rt < rt1; ++rt) {
-    int buf = (rt - rt0) & 1;
-    if (rt + 1 < rt1) stage(buf ^ 1, rt + 1);
+  // one 32-row k-step from the images at img
+  auto compute = [&](const char* img) {
     bf16x8v a_frag[4], b_frag[8];
     #pragma unroll
     for (int i = 0; i < 4; ++i)
-      a_frag[i] = tn_frag(smem + buf * BUF, (wp >> 4) + i, lane);
+      a_frag[i] = tn_frag(img, (wp >> 4) + i, lane);
     if (Asum && q0 == 0 && (wave & 1) == 0) {
       #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -748,15 +761,44 @@ gemm_tn_256_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
     }
     #pragma unroll
     for (int j = 0; j < 8; ++j)
-      b_frag[j] = tn_frag(smem + buf * BUF + IMG, (wq >> 4) + j, lane);
+      b_frag[j] = tn_frag(img + IMG, (wq >> 4) + j, lane);
     #pragma unroll
     for (int i = 0; i < 4; ++i)
       #pragma unroll
       for (int j = 0; j < 8; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
+  };
+
+  if constexpr (RING) {
+    stage(0, rt0);
+    stage(1, rt0 + 1);
+    int buf = 0;
+    for (int rt = rt0; rt < rt1; ++rt) {
+      // stage rt has landed once at most stage rt+1 is still in flight
+      if (rt + 1 < rt1)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      // every wave's share of rt is in LDS, and every wave is done reading
+      // rt-1 (its MFMAs consumed those reads), whose buffer stage rt+2
+      // overwrites
+      raw_barrier();
+      stage(buf == 0 ? 2 : buf - 1, rt + 2);
+      compute(smem + buf * BUF);
+      buf = buf == 2 ? 0 : buf + 1;
+    }
+  } else {
+    stage(0, rt0);
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
+    for (int rt = rt0; rt < rt1; ++rt) {
+      int buf = (rt - rt0) & 1;
+      stage(buf ^ 1, rt + 1);
+      compute(smem + buf * BUF);
+      __builtin_amdgcn_s_waitcnt(0);
+      __syncthreads();
+    }
   }
 
   if (Asum && q0 == 0 && (wave & 1) == 0) {
@@ -789,6 +831,16 @@ gemm_tn_256_kernel(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,
         }
       }
 }
+
+#define TN256_KERNEL(name, ring)                                            \
+  extern "C" __global__ void __launch_bounds__(512)                         \
+  name(const bf16* __restrict__ Ag, const bf16* __restrict__ Bg,            \
+       float* __restrict__ Cw, float* __restrict__ Asum, int R, int P,      \
+       int Q, int splitr, int map_mode) {                                   \
+    tn256_body<ring>(Ag, Bg, Cw, Asum, R, P, Q, splitr, map_mode);          \
+  }
+TN256_KERNEL(gemm_tn_256_kernel, 1)
+TN256_KERNEL(gemm_tn_256_drain_kernel, 0)
 
 // ===========================================================================
 // host wrappers
@@ -896,11 +948,20 @@ gemm_nt_gelu(const at::Tensor& a, const at::Tensor& bt,
 std::tuple<at::Tensor, at::Tensor> gemm_tn_asum(const at::Tensor& a,
                                                 const at::Tensor& b);
 
+// EASYDIST_TN_MAP: 1 = slice-major (default), 0 = tile-major placement,
+// kept for A/B timing.  Read at every launch, not cached in a static, so
+// one process can run both maps.
+static inline int ed_tn_map_mode() {
+  const char* e = getenv("EASYDIST_TN_MAP");
+  return (e && atoi(e) == 0) ? TN_MAP_TILE_MAJOR : TN_MAP_SLICE_MAJOR;
+}
+
 // shared TN launch: picks the 256x256 tile (half the operand re-read
 // traffic) when P and Q allow it AND the grid still covers the chip;
 // falls back to the 128x128 kernel otherwise (edge + small shapes).
 static at::Tensor tn_launch(const at::Tensor& a, const at::Tensor& b,
                             float* asum_p) {
+  const int map_mode = ed_tn_map_mode();
   TORCH_CHECK(a.dtype() == at::kBFloat16 && b.dtype() == at::kBFloat16);
   TORCH_CHECK(a.is_contiguous() && b.is_contiguous());
   const long R = a.size(0), P = a.size(1), Q = b.size(0) == R ? b.size(1) : -1;
@@ -929,6 +990,10 @@ static at::Tensor tn_launch(const at::Tensor& a, const at::Tensor& b,
       return e ? atoi(e) : 256;
     }();
     splitr = std::max(1, target / (int)ntile);
+    // EASYDIST_TN256_SPLITR forces the split (tuning sweeps); read at
+    // every launch like the map mode
+    if (const char* e = getenv("EASYDIST_TN256_SPLITR"))
+      if (atoi(e) > 0) splitr = atoi(e);
     splitr = std::min((long)splitr, R / TBR / 8);   // >=8 k-steps per slice
     splitr = std::max(1, std::min(splitr, 64));
   } else {
@@ -943,17 +1008,24 @@ static at::Tensor tn_launch(const at::Tensor& a, const at::Tensor& b,
       : at::zeros({P, Q}, a.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
   if (big) {
-    size_t lds = 2 * 2 * TBR * TBP2 * 2;   // 64 KiB
-    hipLaunchKernelGGL(gemm_tn_256_kernel, dim3(ntile * splitr), dim3(512),
+    // EASYDIST_TN256_STAGING: 1 = three-buffer ring (default), 0 = the
+    // old issue-then-drain loop, kept for A/B; read at every launch
+    const char* se = getenv("EASYDIST_TN256_STAGING");
+    const bool ring = !(se && atoi(se) == 0);
+    auto kern = ring ? gemm_tn_256_kernel : gemm_tn_256_drain_kernel;
+    size_t lds = (ring ? 3 : 2) * 2 * TBR * TBP2 * 2;   // 96 / 64 KiB
+    hipLaunchKernelGGL(kern, dim3(ntile * splitr), dim3(512),
         lds, stream,
         (const bf16*)a.data_ptr(), (const bf16*)b.data_ptr(),
-        cw.data_ptr<float>(), asum_p, (int)R, (int)P, (int)Q, splitr);
+        cw.data_ptr<float>(), asum_p, (int)R, (int)P, (int)Q, splitr,
+        map_mode);
   } else {
     size_t lds = 2 * 2 * TBR * TBP * 2;   // 32 KiB
     hipLaunchKernelGGL(gemm_tn_kernel, dim3(ntile * splitr), dim3(256), lds,
         stream,
         (const bf16*)a.data_ptr(), (const bf16*)b.data_ptr(),
-        cw.data_ptr<float>(), asum_p, (int)R, (int)P, (int)Q, splitr);
+        cw.data_ptr<float>(), asum_p, (int)R, (int)P, (int)Q, splitr,
+        map_mode);
   }
   return cw;
 }
