@@ -1,13 +1,19 @@
-// Flash attention forward for gfx950 (bf16, causal, D in {64, 128}).
+// Flash attention forward and backward for gfx950 (bf16, causal or full,
+// D in {64, 128}).
 //
-// v1 structure (correctness-first; the tuned ladder of
-// cdna_hip_programming.md §B comes in later rounds): one workgroup = 4
-// waves = one 64-row Q block of one (batch, head). Each wave owns 16 Q
-// rows. K/V tiles (64 keys x D) are staged in LDS per workgroup; QK^T and
-// P·V run on v_mfma_f32_16x16x32_bf16; the online-softmax state (m, l)
-// lives in registers, row-reductions via 16-lane shuffles inside each
-// fragment group. P round-trips through a wave-private LDS strip to
-// re-fragment from the S layout to the PV A-operand layout.
+// All four kernels share one structure: one workgroup = 8 waves = one
+// 128-row block (q rows in fwd/dq, keys in dkv) of one (batch, head),
+// placed on the chip by attn_block_map; each wave owns 16 rows.  The
+// 64-row tiles of the other operand pair are register-prefetched from
+// global memory and double-buffered in LDS under the lsw swizzle; every
+// product runs on v_mfma_f32_16x16x32_bf16.
+//
+// fwd and dq compute the SWAPPED-operand S^T = K Q^T, so each lane holds
+// one q row: the online-softmax state (m, l) is one register pair per
+// lane, row reductions are in-register plus two cross-group shuffles, and
+// P / dS reach the next MFMA's A-operand layout through an in-register
+// butterfly (swp_pack + swp_butterfly) with no LDS round-trip.  dkv ships
+// un-swapped, re-fragmenting through a wave-private LDS strip.
 #include "common.h"
 #include "attn_block_map.h"
 #include <torch/extension.h>
@@ -17,12 +23,8 @@
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using bf16x8v = __attribute__((ext_vector_type(8))) __bf16;
 
-#define QB 64     // q rows per workgroup (16 per wave)
-#define KB 64     // kv tile
-#define KBP (KB + 8)  // padded stride for transposed tiles: row stride
-                      // 144 B spreads the 64 LDS banks (unpadded 128 B
-                      // collapses onto 2 banks -> 8-way conflicts)
-#define QBP (QB + 8)
+#define QB 64     // q tile (dkv); fwd/dq workgroups own 2*QB q rows
+#define KB 64     // kv tile (fwd/dq); dkv workgroups own 2*KB keys
 
 // Bank-conflict XOR swizzle for LINEAR [rows][64 or 128] bf16 LDS tiles
 // (element-index form): a ds_read_b128 fragment read walks 16 rows at a
@@ -72,21 +74,17 @@ DEVINL bf16x8v swp_butterfly(const unsigned pk[][2], int ks, int fg) {
   return cv.v;
 }
 
-// SW=1 (swapped-operand form): QK^T runs as K*Q^T so the C-layout puts
-// ONE q row per lane (col = l&15 = qrow, regs = 16 keys). The online
-// softmax then reduces over REGISTERS (15 VALU max/add) plus TWO
-// shuffles (xor 16/32 across the fg groups) instead of four dependent
-// 4-level shuffle trees, and P reaches the PV A-operand layout through
-// a 12-shuffle in-register butterfly (v_cvt_pk_bf16_f32 pairs exchanged
-// at xor distances 16/32/48) instead of an LDS strip round-trip.
-// Derivation: key K = 16j + 4g_src + r = 32ks + 8g_tgt + u maps source
-// group g_src = (K>>2)&3 to target group g_tgt = (K>>3)&3; each target
-// half-fragment (4 keys) is one source lane's consecutive regs, so per
-// ks three selected-send exchanges (xor16: g0<-g1/g3<-g2, xor32:
-// g1<-g3/g2<-g0, xor48: g1<-g2/g2<-g1) deliver every piece.
-template <int D, int RF = 1, int KD = 0, int SW = 0>
+// Swapped-operand form: QK^T runs as K*Q^T so the C-layout puts ONE q row
+// per lane (col = l&15 = qrow, regs = 16 keys). The online softmax then
+// reduces over REGISTERS (15 VALU max/add) plus TWO shuffles (xor 16/32
+// across the fg groups) instead of four dependent 4-level shuffle trees,
+// and P reaches the PV A-operand layout through the 12-shuffle in-register
+// butterfly above instead of an LDS strip round-trip.  The un-swapped
+// strip form, a 256-row (two fragments per wave) block and direct-from-L2
+// K reads were all A/B'd on hardware and lost (profiles/README.md).
+template <int D>
 __global__ void
-__launch_bounds__(512, (D == 64 ? (RF == 1 ? 4 : 3) : 1))  // waves/SIMD floor
+__launch_bounds__(512, (D == 64 ? 4 : 1))  // waves/SIMD floor
 flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                  const bf16* __restrict__ V, bf16* __restrict__ O,
                  float* __restrict__ LSE, int B, int H, int S, bool causal,
@@ -94,14 +92,11 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                  long qsb, long qsh, long qss, long ksb, long ksh, long kss,
                  long vsb, long vsh, long vss, int map_mode) {
   // grid: 1-D, ceil(S/QBLK) * B*H workgroups placed by attn_block_map
-  // (attn_block_map.h); QBLK = 128*RF q rows per workgroup, 8
-  // waves of RF 16-row fragments each.  The round-1 4-wave/256-thread
-  // form ran ONE wave per SIMD (110 KB LDS) — every softmax/LDS stall
-  // fully exposed, ~100 TF effective.  8 waves + the smaller strip pool
-  // give 4 waves/SIMD at D=64/RF=1.  RF=2 doubles the q rows sharing
-  // each staged K/V tile (half the staging + barrier cost per flop) at
-  // one wave/SIMD lower occupancy — A/B'd on hardware.
-  constexpr int QBLK = 8 * 16 * RF;
+  // (attn_block_map.h); 8 waves of one 16-row fragment each.  The round-1
+  // 4-wave/256-thread form ran ONE wave per SIMD (110 KB LDS) — every
+  // softmax/LDS stall fully exposed, ~100 TF effective.  8 waves + the
+  // smaller LDS footprint give 4 waves/SIMD at D=64.
+  constexpr int QBLK = 2 * QB;
   const AttnBlock wgm = attn_block_map(blockIdx.x, (S + QBLK - 1) / QBLK,
                                        B * H, causal, map_mode);
   const int qb0 = wgm.blk * QBLK;
@@ -119,71 +114,55 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
   const int lane = threadIdx.x % WAVE;
   const int wave = threadIdx.x / WAVE;
 
-  // LDS: DOUBLE-BUFFERED K [KB][D] + V^T [D][KB] (lsw) pairs + P strips.
+  // LDS: DOUBLE-BUFFERED K [KB][D] + V^T [D][KB] (lsw) pairs.
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TILE_K = KB * D;
   constexpr int TILE_VT = KB * D;   // [D][KB] linear + lsw swizzle
   bf16* smem_b = reinterpret_cast<bf16*>(smem);
-  bf16* p_lds = smem_b + 2 * (TILE_K + TILE_VT) + wave * 16 * KB;
   constexpr int NTHR = 8 * WAVE;   // 512
 
   const int fr = lane & 15;        // fragment row/col index
   const int fg = lane >> 4;        // fragment k-group (8 contiguous)
 
-  // per-fragment first q row (two contiguous 16-row fragments per wave)
-  int qr0[RF];
-  #pragma unroll
-  for (int rf = 0; rf < RF; ++rf) qr0[rf] = qb0 + wave * 16 * RF + rf * 16;
+  const int qr0 = qb0 + wave * 16; // this wave's first q row
+  const int qrow = qr0 + fr;       // this lane's q row
 
-  // Q fragments (A operand), PRE-SCALED by scale*log2(e): the softmax
-  // runs in exp2 domain (v_exp2 without the fused multiply) and the hot
-  // loop loses its per-element scale multiply
+  // Q fragments (B operand of S^T), PRE-SCALED by scale*log2(e): the
+  // softmax runs in exp2 domain (v_exp2 without the fused multiply) and
+  // the hot loop loses its per-element scale multiply
   const float qscale = scale * 1.44269504088896340736f;
-  bf16x8v qf[RF][D / 32];
+  bf16x8v qf[D / 32];
   #pragma unroll
-  for (int rf = 0; rf < RF; ++rf) {
-    const int row = qr0[rf] + fr;
-    #pragma unroll
-    for (int ks = 0; ks < D / 32; ++ks) {
-      if (row < S) {
-        bf16x8v raw = *reinterpret_cast<const bf16x8v*>(
-            &q[(long)row * qss + ks * 32 + fg * 8]);
-        #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          qf[rf][ks][u] = (__bf16)(bf2f((bf16)raw[u]) * qscale);
-      } else {
-        #pragma unroll
-        for (int u = 0; u < 8; ++u) qf[rf][ks][u] = (__bf16)0.f;
-      }
+  for (int ks = 0; ks < D / 32; ++ks) {
+    if (qrow < S) {
+      bf16x8v raw = *reinterpret_cast<const bf16x8v*>(
+          &q[(long)qrow * qss + ks * 32 + fg * 8]);
+      #pragma unroll
+      for (int u = 0; u < 8; ++u)
+        qf[ks][u] = (__bf16)(bf2f((bf16)raw[u]) * qscale);
+    } else {
+      #pragma unroll
+      for (int u = 0; u < 8; ++u) qf[ks][u] = (__bf16)0.f;
     }
   }
 
-  float m_run[RF][4], l_run[RF][4];
-  f32x4 o_acc[RF][D / 16];
+  // softmax state of THIS LANE's q row; o_acc rows are qrows 4*fg+r
+  float m_run = -1e30f, l_run = 0.f;
+  f32x4 o_acc[D / 16];
   #pragma unroll
-  for (int rf = 0; rf < RF; ++rf) {
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) { m_run[rf][r] = -1e30f; l_run[rf][r] = 0.f; }
-    #pragma unroll
-    for (int j = 0; j < D / 16; ++j) o_acc[rf][j] = {0.f, 0.f, 0.f, 0.f};
-  }
+  for (int j = 0; j < D / 16; ++j) o_acc[j] = {0.f, 0.f, 0.f, 0.f};
 
   const int kv_end = causal ? min(S, qb0 + QBLK) : S;
   const int n_tiles = (kv_end + KB - 1) / KB;
   constexpr int PF = TILE_K / (NTHR * 8);    // 16B vectors per thread
   bf16x8 kreg[PF], vreg[PF];
 
-  // KD=1: K fragments are read straight from global memory (the per-
-  // (b,h) K slab is L2-resident at these shapes) — no K staging, no
-  // K-tile LDS reads, and the tile barrier only covers the V transpose
   auto load_tile = [&](int t) {
     #pragma unroll
     for (int pi = 0; pi < PF; ++pi) {
       const int e = threadIdx.x * 8 + pi * (NTHR * 8);
       const int row = t * KB + e / D, col = e % D;
-      if (!KD)
-        kreg[pi] = *reinterpret_cast<const bf16x8*>(
-            &k[(long)row * kss + col]);
+      kreg[pi] = *reinterpret_cast<const bf16x8*>(&k[(long)row * kss + col]);
       vreg[pi] = *reinterpret_cast<const bf16x8*>(&v[(long)row * vss + col]);
     }
   };
@@ -193,8 +172,7 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
     #pragma unroll
     for (int pi = 0; pi < PF; ++pi) {
       const int e = threadIdx.x * 8 + pi * (NTHR * 8);
-      if (!KD)
-        *reinterpret_cast<bf16x8*>(&kb[lsw(e)]) = kreg[pi];
+      *reinterpret_cast<bf16x8*>(&kb[lsw(e)]) = kreg[pi];
       const int row = e / D, col = e % D;
       #pragma unroll
       for (int i = 0; i < 8; ++i)
@@ -213,95 +191,12 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
     if (t + 1 < n_tiles)
       load_tile(t + 1);          // global loads overlap the MFMA loop
 
-    // a 128*RF-row block spans 8 waves: tiles strictly above this wave's
+    // a 128-row block spans 8 waves: tiles strictly above this wave's
     // causal diagonal are all-masked — skip the compute (NOT the
     // barriers: every wave still arrives at __syncthreads)
-    const bool wave_active = !(causal && kv0 > qr0[RF - 1] + 15);
+    const bool wave_active = !(causal && kv0 > qr0 + 15);
     if (wave_active) {
-    #pragma unroll
-    for (int rf = 0; rf < RF; ++rf) {
-      if (RF > 1 && causal && kv0 > qr0[rf] + 15)
-        continue;                  // this fragment's rows are all-masked
-      if (SW) {
-        // ---- S^T = K Q^T: lane col = qrow, regs = 16 keys -------------
-        f32x4 s_acc[KB / 16];
-        __builtin_amdgcn_s_setprio(1);
-        #pragma unroll
-        for (int j = 0; j < KB / 16; ++j) {
-          s_acc[j] = {0.f, 0.f, 0.f, 0.f};
-          #pragma unroll
-          for (int ks = 0; ks < D / 32; ++ks) {
-            bf16x8v kf = *reinterpret_cast<const bf16x8v*>(
-                &k_lds[lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
-            s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                kf, qf[rf][ks], s_acc[j], 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        const int qrow = qr0[rf] + fr;
-        const bool need_mask = (causal && kv0 + KB - 1 > qrow)
-                               || (kv0 + KB > S);
-        float mx = -1e30f;
-        if (need_mask) {
-          #pragma unroll
-          for (int j = 0; j < KB / 16; ++j)
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int kcol = kv0 + j * 16 + 4 * fg + r;
-              float sv = s_acc[j][r];
-              if ((causal && kcol > qrow) || kcol >= S) sv = -1e30f;
-              s_acc[j][r] = sv;
-              mx = fmaxf(mx, sv);
-            }
-        } else {
-          #pragma unroll
-          for (int j = 0; j < KB / 16; ++j)
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s_acc[j][r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
-        float m_new = fmaxf(m_run[rf][0], mx);
-        float psum = 0.f;
-        #pragma unroll
-        for (int j = 0; j < KB / 16; ++j)
-          #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float pp = __builtin_amdgcn_exp2f(s_acc[j][r] - m_new);
-            s_acc[j][r] = pp;
-            psum += pp;
-          }
-        psum += __shfl_xor(psum, 16, WAVE);
-        psum += __shfl_xor(psum, 32, WAVE);
-        float alpha = __builtin_amdgcn_exp2f(m_run[rf][0] - m_new);
-        l_run[rf][0] = l_run[rf][0] * alpha + psum;
-        m_run[rf][0] = m_new;
-        // o_acc rows are qrows 4*fg+r: fetch those rows' alpha
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float ar = __shfl(alpha, 4 * fg + r, WAVE);
-          #pragma unroll
-          for (int j = 0; j < D / 16; ++j) o_acc[rf][j][r] *= ar;
-        }
-        // pack to bf16 pairs and run the butterfly (swp_* helpers)
-        unsigned pk[KB / 16][2];
-        swp_pack(s_acc, KB / 16, pk);
-        __builtin_amdgcn_s_setprio(1);
-        #pragma unroll
-        for (int ks = 0; ks < KB / 32; ++ks) {
-          bf16x8v pv = swp_butterfly(pk, ks, fg);
-          #pragma unroll
-          for (int j = 0; j < D / 16; ++j) {
-            bf16x8v vf = *reinterpret_cast<const bf16x8v*>(
-                &vt_lds[lsw((j * 16 + fr) * KB + ks * 32 + fg * 8)]);
-            o_acc[rf][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                pv, vf, o_acc[rf][j], 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        continue;                  // SW path done for this fragment
-      }
-      // ---- S = Q K^T ----------------------------------------------------
+      // ---- S^T = K Q^T: lane col = qrow, regs = 16 keys ---------------
       f32x4 s_acc[KB / 16];
       __builtin_amdgcn_s_setprio(1);
       #pragma unroll
@@ -309,104 +204,76 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
         s_acc[j] = {0.f, 0.f, 0.f, 0.f};
         #pragma unroll
         for (int ks = 0; ks < D / 32; ++ks) {
-          bf16x8v kf;
-          if (KD)
-            kf = *reinterpret_cast<const bf16x8v*>(
-                &k[(long)(kv0 + j * 16 + fr) * kss + ks * 32 + fg * 8]);
-          else
-            kf = *reinterpret_cast<const bf16x8v*>(
-                &k_lds[lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
-          s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[rf][ks], kf,
-                                                             s_acc[j], 0, 0,
-                                                             0);
+          bf16x8v kf = *reinterpret_cast<const bf16x8v*>(
+              &k_lds[lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+          s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              kf, qf[ks], s_acc[j], 0, 0, 0);
         }
       }
       __builtin_amdgcn_s_setprio(0);
-
-      // ---- online softmax ----------------------------------------------
+      // ---- online softmax ---------------------------------------------
       // interior tiles (fully below the causal diagonal, fully in-range)
       // skip the per-element mask compares — most tiles at long S
-      const bool need_mask = (causal && kv0 + KB - 1 > qr0[rf] + 4 * fg)
+      const bool need_mask = (causal && kv0 + KB - 1 > qrow)
                              || (kv0 + KB > S);
-      float m_new[4];
+      float mx = -1e30f;
       if (need_mask) {
         #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float mx = -1e30f;
+        for (int j = 0; j < KB / 16; ++j)
           #pragma unroll
-          for (int j = 0; j < KB / 16; ++j) {
+          for (int r = 0; r < 4; ++r) {
+            int kcol = kv0 + j * 16 + 4 * fg + r;
             float sv = s_acc[j][r];        // already scale*log2e scaled
-            int kcol = kv0 + j * 16 + fr;
-            int qrow = qr0[rf] + 4 * fg + r;
-            if (causal && kcol > qrow) sv = -1e30f;
-            else if (kcol >= S) sv = -1e30f;
+            if ((causal && kcol > qrow) || kcol >= S) sv = -1e30f;
             s_acc[j][r] = sv;
             mx = fmaxf(mx, sv);
           }
-          #pragma unroll
-          for (int off = 8; off > 0; off >>= 1)
-            mx = fmaxf(mx, __shfl_xor(mx, off, WAVE));
-          m_new[r] = fmaxf(m_run[rf][r], mx);
-        }
       } else {
         #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float mx = fmaxf(fmaxf(s_acc[0][r], s_acc[1][r]),
-                           fmaxf(s_acc[2][r], s_acc[3][r]));
+        for (int j = 0; j < KB / 16; ++j)
           #pragma unroll
-          for (int off = 8; off > 0; off >>= 1)
-            mx = fmaxf(mx, __shfl_xor(mx, off, WAVE));
-          m_new[r] = fmaxf(m_run[rf][r], mx);
-        }
+          for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s_acc[j][r]);
       }
-      float p_sum[4] = {0.f, 0.f, 0.f, 0.f};
-      #pragma unroll
-      for (int j = 0; j < KB / 16; ++j) {
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float pp = __builtin_amdgcn_exp2f(s_acc[j][r] - m_new[r]);
-          s_acc[j][r] = pp;
-          p_sum[r] += pp;
-        }
-      }
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        #pragma unroll
-        for (int off = 8; off > 0; off >>= 1)
-          p_sum[r] += __shfl_xor(p_sum[r], off, WAVE);
-        float alpha = __builtin_amdgcn_exp2f(m_run[rf][r] - m_new[r]);
-        l_run[rf][r] = l_run[rf][r] * alpha + p_sum[r];
-        m_run[rf][r] = m_new[r];
-        #pragma unroll
-        for (int j = 0; j < D / 16; ++j) o_acc[rf][j][r] *= alpha;
-      }
-
-      // ---- P through the wave strip, then P @ V -------------------------
+      mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
+      float m_new = fmaxf(m_run, mx);
+      float psum = 0.f;
       #pragma unroll
       for (int j = 0; j < KB / 16; ++j)
         #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          p_lds[lsw((4 * fg + r) * KB + j * 16 + fr)] = f2bf(s_acc[j][r]);
-      lds_fence();
-      bf16x8v pf[KB / 32];
+        for (int r = 0; r < 4; ++r) {
+          float pp = __builtin_amdgcn_exp2f(s_acc[j][r] - m_new);
+          s_acc[j][r] = pp;
+          psum += pp;
+        }
+      psum += __shfl_xor(psum, 16, WAVE);
+      psum += __shfl_xor(psum, 32, WAVE);
+      float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      l_run = l_run * alpha + psum;
+      m_run = m_new;
+      // o_acc rows are qrows 4*fg+r: fetch those rows' alpha
       #pragma unroll
-      for (int ks = 0; ks < KB / 32; ++ks)
-        pf[ks] = *reinterpret_cast<const bf16x8v*>(
-            &p_lds[lsw(fr * KB + ks * 32 + fg * 8)]);
-      lds_fence();   // strip is reused by the next fragment
+      for (int r = 0; r < 4; ++r) {
+        float ar = __shfl(alpha, 4 * fg + r, WAVE);
+        #pragma unroll
+        for (int j = 0; j < D / 16; ++j) o_acc[j][r] *= ar;
+      }
+      // ---- P through the butterfly, then P @ V ------------------------
+      unsigned pk[KB / 16][2];
+      swp_pack(s_acc, KB / 16, pk);
       __builtin_amdgcn_s_setprio(1);
       #pragma unroll
-      for (int j = 0; j < D / 16; ++j) {
+      for (int ks = 0; ks < KB / 32; ++ks) {
+        bf16x8v pv = swp_butterfly(pk, ks, fg);
         #pragma unroll
-        for (int ks = 0; ks < KB / 32; ++ks) {
+        for (int j = 0; j < D / 16; ++j) {
           bf16x8v vf = *reinterpret_cast<const bf16x8v*>(
               &vt_lds[lsw((j * 16 + fr) * KB + ks * 32 + fg * 8)]);
-          o_acc[rf][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              pf[ks], vf, o_acc[rf][j], 0, 0, 0);
+          o_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              pv, vf, o_acc[j], 0, 0, 0);
         }
       }
       __builtin_amdgcn_s_setprio(0);
-    }
     }
 
     if (t + 1 < n_tiles)
@@ -415,40 +282,20 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
   }
 
   // ---- epilogue --------------------------------------------------------
+  // o_acc rows need the row-owners' 1/l via shuffle
+  float invl = 1.f / l_run;
   #pragma unroll
-  for (int rf = 0; rf < RF; ++rf) {
-    if (SW) {
-      // softmax state lives per lane (col = qrow); o_acc rows need the
-      // row-owners' 1/l via shuffle
-      float invl = 1.f / l_run[rf][0];
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int qrow = qr0[rf] + 4 * fg + r;
-        if (qrow >= S) continue;
-        float ir = __shfl(invl, 4 * fg + r, WAVE);
-        #pragma unroll
-        for (int j = 0; j < D / 16; ++j)
-          o[(long)qrow * D + j * 16 + fr] = f2bf(o_acc[rf][j][r] * ir);
-      }
-      int myrow = qr0[rf] + fr;
-      if (fg == 0 && myrow < S)
-        lse[myrow] = 0.69314718055994530942f
-                     * (m_run[rf][0] + __log2f(l_run[rf][0]));
-      continue;
-    }
+  for (int r = 0; r < 4; ++r) {
+    int orow = qr0 + 4 * fg + r;
+    if (orow >= S) continue;
+    float ir = __shfl(invl, 4 * fg + r, WAVE);
     #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int qrow = qr0[rf] + 4 * fg + r;
-      if (qrow >= S) continue;
-      float inv_l = 1.f / l_run[rf][r];
-      #pragma unroll
-      for (int j = 0; j < D / 16; ++j)
-        o[(long)qrow * D + j * 16 + fr] = f2bf(o_acc[rf][j][r] * inv_l);
-      if (fr == 0)   // m_run is log2-domain: lse = ln(sum exp) = ln2*(m2 + log2 l)
-        lse[qrow] = 0.69314718055994530942f
-                    * (m_run[rf][r] + __log2f(l_run[rf][r]));
-    }
+    for (int j = 0; j < D / 16; ++j)
+      o[(long)orow * D + j * 16 + fr] = f2bf(o_acc[j][r] * ir);
   }
+  // m_run is log2-domain: lse = ln(sum exp) = ln2*(m2 + log2 l)
+  if (fg == 0 && qrow < S)
+    lse[qrow] = 0.69314718055994530942f * (m_run + __log2f(l_run));
 }
 
 // accept any 4-D view with a contiguous last dim (e.g. the [B,S,H,D]
@@ -486,31 +333,15 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
   auto out = at::empty({B, H, S, D}, q.options());
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
-  static int rf = []() {
-    const char* e = getenv("EASYDIST_FWD_RF");
-    return e ? atoi(e) : 1;
-  }();
-  static int kd = []() {
-    const char* e = getenv("EASYDIST_FWD_KDIRECT");
-    return e ? atoi(e) : 0;
-  }();
-  static int sw = []() {   // default ON: -17% (D=64) / -12% (D=128) A/B'd
-    const char* e = getenv("EASYDIST_FWD_SWAP");
-    return e ? atoi(e) : 1;
-  }();
-  const int use_rf = (rf == 2 && S % 256 == 0) ? 2 : 1;
-  dim3 grid = ed_attn_grid((S + 128 * use_rf - 1) / (128 * use_rf),
-                           (long)B * H, "flash_attn_fwd"), block(512);
+  dim3 grid = ed_attn_grid((S + 2 * QB - 1) / (2 * QB), (long)B * H,
+                           "flash_attn_fwd"), block(512);
   const int map_mode = ed_attn_map_mode();
+  // the trailing 8 * 16 * KB strip elements are unused since the strip
+  // form left; LDS size sets workgroups per CU, so reclaiming them needs a
+  // measured change
   size_t lds = (2 * ((size_t)KB * D + (size_t)KB * D) + 8 * 16 * KB) * 2;
   float scale = 1.f / sqrtf((float)D);
-  auto kern = (D == 64)
-      ? (use_rf == 2 ? flash_fwd_kernel<64, 2>
-         : sw ? flash_fwd_kernel<64, 1, 0, 1>
-         : kd ? flash_fwd_kernel<64, 1, 1> : flash_fwd_kernel<64, 1>)
-      : (use_rf == 2 ? flash_fwd_kernel<128, 2>
-         : sw ? flash_fwd_kernel<128, 1, 0, 1>
-         : kd ? flash_fwd_kernel<128, 1, 1> : flash_fwd_kernel<128, 1>);
+  auto kern = (D == 64) ? flash_fwd_kernel<64> : flash_fwd_kernel<128>;
   hipLaunchKernelGGL(kern, grid, block, lds, stream,
       (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
       (const bf16*)v.data_ptr(), (bf16*)out.data_ptr(),
@@ -523,9 +354,9 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
 
 // ---------------------------------------------------------------------------
 // Flash attention backward: two kernels, no atomics.
-//   dq kernel: one workgroup per 64-row Q block; recomputes P from lse,
+//   dq kernel: one workgroup per 128-row Q block; recomputes P from lse,
 //     dP = dO V^T, dS = P (dP - delta) scale, dq += dS K.
-//   dkv kernel: one workgroup per 64-key KV block; recomputes P^T,
+//   dkv kernel: one workgroup per 128-key KV block; recomputes P^T,
 //     dV += P^T dO, dP^T = V dO^T, dS^T = P^T (dP^T - delta) scale,
 //     dK += dS^T Q.
 // delta = rowsum(dO * O) comes precomputed from the host (one fused
@@ -534,7 +365,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
 // hold row fr, k-slice fg; C/D lanes hold row 4*fg+r, col fr.
 // ---------------------------------------------------------------------------
 
-template <int D, int SW = 0>
+template <int D>
 __global__ void __launch_bounds__(512)
 flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -578,8 +409,6 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   bf16* k_lds = reinterpret_cast<bf16*>(smem);     // + buf * DQBUF
   bf16* v_lds = k_lds + KB * D;
   bf16* kt_lds = v_lds + KB * D;                   // K^T [D][KB] + lsw
-  bf16* s_lds = reinterpret_cast<bf16*>(smem) + 2 * DQBUF
-                + wave * 16 * KB;                   // wave-private strip
 
   // A-operand fragments for this wave's 16 q rows
   bf16x8v qf[D / 32], dof[D / 32];
@@ -590,19 +419,10 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     dof[ks] = *reinterpret_cast<const bf16x8v*>(
         &dO_[(long)(qr0 + fr) * dss + ks * 32 + fg * 8]);
   }
-  // per C-row lse/delta (rows 4*fg+r; SW: one row per lane = fr)
-  float lse_r[4], dlt_r[4];
-  if (!SW) {
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int qrow = qr0 + 4 * fg + r;
-      lse_r[r] = lse[qrow];
-      dlt_r[r] = delta[qrow];
-    }
-  } else {
-    lse_r[0] = lse[qr0 + fr];
-    dlt_r[0] = delta[qr0 + fr];
-  }
+  // swapped operands below: one q row per lane, so one lse/delta each
+  const int qrow = qr0 + fr;
+  const float lse_r = lse[qrow];
+  const float dlt_r = delta[qrow];
 
   f32x4 dq_acc[D / 16];
   #pragma unroll
@@ -651,8 +471,8 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       continue;
     }
 
-    // S(^T) = Q K^T and dP(^T) = dO V^T: SW=1 swaps operands so the
-    // C-layout holds ONE q row per lane (col = fr) with 16 keys in regs
+    // S^T = K Q^T and dP^T = V dO^T: the swapped operands make the
+    // C-layout hold ONE q row per lane (col = fr) with 16 keys in regs
     f32x4 s_acc[KB / 16], dp_acc[KB / 16];
     #pragma unroll
     for (int j = 0; j < KB / 16; ++j) {
@@ -664,78 +484,32 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
             &k_lds[bofs + lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
         bf16x8v vf = *reinterpret_cast<const bf16x8v*>(
             &v_lds[bofs + lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
-        if (SW) {
-          s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              kf, qf[ks], s_acc[j], 0, 0, 0);
-          dp_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              vf, dof[ks], dp_acc[j], 0, 0, 0);
-        } else {
-          s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              qf[ks], kf, s_acc[j], 0, 0, 0);
-          dp_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              dof[ks], vf, dp_acc[j], 0, 0, 0);
-        }
+        s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            kf, qf[ks], s_acc[j], 0, 0, 0);
+        dp_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            vf, dof[ks], dp_acc[j], 0, 0, 0);
       }
     }
     // dS = P * (dP - delta) * scale, P = exp(S*scale - lse)
-    bf16x8v dsf[KB / 32];
-    if (SW) {
-      const int qrow = qr0 + fr;
-      const bool need_mask = (causal && kv0 + KB - 1 > qrow)
-                             || (kv0 + KB > S);
-      #pragma unroll
-      for (int j = 0; j < KB / 16; ++j)
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float p = 0.f;
-          int kcol = kv0 + j * 16 + 4 * fg + r;
-          if (!need_mask || (!(causal && kcol > qrow) && kcol < S))
-            p = __expf(s_acc[j][r] * scale - lse_r[0]);
-          s_acc[j][r] = p * (dp_acc[j][r] - dlt_r[0]) * scale;
-        }
-      unsigned pk[KB / 16][2];
-      swp_pack(s_acc, KB / 16, pk);
-      #pragma unroll
-      for (int ks = 0; ks < KB / 32; ++ks)
-        dsf[ks] = swp_butterfly(pk, ks, fg);
-    } else {
-    const bool need_mask = (causal && kv0 + KB - 1 > qr0 + 4 * fg)
+    const bool need_mask = (causal && kv0 + KB - 1 > qrow)
                            || (kv0 + KB > S);
-    if (need_mask) {
-      #pragma unroll
-      for (int j = 0; j < KB / 16; ++j) {
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int kcol = kv0 + j * 16 + fr;
-          int qrow = qr0 + 4 * fg + r;
-          float p = 0.f;
-          if (!(causal && kcol > qrow) && kcol < S)
-            p = __expf(s_acc[j][r] * scale - lse_r[r]);
-          s_acc[j][r] = p * (dp_acc[j][r] - dlt_r[r]) * scale;
-        }
-      }
-    } else {
-      #pragma unroll
-      for (int j = 0; j < KB / 16; ++j) {
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float p = __expf(s_acc[j][r] * scale - lse_r[r]);
-          s_acc[j][r] = p * (dp_acc[j][r] - dlt_r[r]) * scale;
-        }
-      }
-    }
-    // re-fragment dS through the wave strip
     #pragma unroll
     for (int j = 0; j < KB / 16; ++j)
       #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        s_lds[lsw((4 * fg + r) * KB + j * 16 + fr)] = f2bf(s_acc[j][r]);
-    lds_fence();
+      for (int r = 0; r < 4; ++r) {
+        float p = 0.f;
+        int kcol = kv0 + j * 16 + 4 * fg + r;
+        if (!need_mask || (!(causal && kcol > qrow) && kcol < S))
+          p = __expf(s_acc[j][r] * scale - lse_r);
+        s_acc[j][r] = p * (dp_acc[j][r] - dlt_r) * scale;
+      }
+    // dS to the A-operand layout in-register (no strip, no fences)
+    bf16x8v dsf[KB / 32];
+    unsigned pk[KB / 16][2];
+    swp_pack(s_acc, KB / 16, pk);
     #pragma unroll
     for (int ks = 0; ks < KB / 32; ++ks)
-      dsf[ks] = *reinterpret_cast<const bf16x8v*>(
-          &s_lds[lsw(fr * KB + ks * 32 + fg * 8)]);
-    }
+      dsf[ks] = swp_butterfly(pk, ks, fg);
     // dq += dS @ K: B-operand from K^T — contiguous vector loads
     #pragma unroll
     for (int j = 0; j < D / 16; ++j) {
@@ -753,11 +527,11 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   }
   #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    int qrow = qr0 + 4 * fg + r;
-    if (qrow >= S) continue;
+    int orow = qr0 + 4 * fg + r;
+    if (orow >= S) continue;
     #pragma unroll
     for (int j = 0; j < D / 16; ++j)
-      dq[(long)qrow * oss + j * 16 + fr] = f2bf(dq_acc[j][r]);
+      dq[(long)orow * oss + j * 16 + fr] = f2bf(dq_acc[j][r]);
   }
 }
 
@@ -1090,18 +864,14 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   dim3 grid = ed_attn_grid(S / (2 * QB), (long)B * H, "flash_attn_bwd"),
        block(512);
   const int map_mode = ed_attn_map_mode();
-  // dq: DOUBLE-buffered (K+V+K^T) tiles + wave strips
+  // dq: DOUBLE-buffered (K+V+K^T) tiles.  The trailing 8 * 16 * KB strip
+  // elements are unused since the strip form left; LDS size sets workgroups
+  // per CU, so reclaiming them needs a measured change
   size_t lds = (2 * (3 * (size_t)KB * D) + 8 * 16 * KB) * 2;
   // dkv: DOUBLE-buffered (Q+dO+Q^T+dO^T) tiles + wave strips
   size_t lds_kv = (2 * (4 * (size_t)QB * D) + 8 * 16 * QB) * 2;
   float scale = 1.f / sqrtf((float)D);
-  static int swb = []() {   // swapped-operand dq (butterfly dS transport)
-    const char* e = getenv("EASYDIST_BWD_SWAP");
-    return e ? atoi(e) : 1;
-  }();
-  auto qkern = (D == 64)
-      ? (swb ? flash_bwd_dq_kernel<64, 1> : flash_bwd_dq_kernel<64>)
-      : (swb ? flash_bwd_dq_kernel<128, 1> : flash_bwd_dq_kernel<128>);
+  auto qkern = (D == 64) ? flash_bwd_dq_kernel<64> : flash_bwd_dq_kernel<128>;
   static int swkv = []() {  // dkv butterfly measured SLOWER than the
     const char* e = getenv("EASYDIST_DKV_SWAP");   // strip (2.11 vs 1.74
     return e ? atoi(e) : 0;                        // ms) — default off

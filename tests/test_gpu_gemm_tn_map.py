@@ -10,12 +10,15 @@ up as a wrong integer; the split-R workspace is zero-filled, so an
 unvisited tile reads as zero (no reference here has an all-zero 256x256
 tile: checked on the CPU for these seeds, and asserted below).
 
-The older TN tests never reach gemm_tn_256_kernel with a split (it needs
-R >= 2048 and P, Q >= 256); these are the smallest shapes that do.  The
+Both tile sizes are instantiations of one kernel template.  The older TN
+tests never reach gemm_tn_256_kernel with a split (it needs R >= 2048 and
+P, Q >= 256); the shapes with P, Q >= 256 are the smallest that do.  The
 256-tile kernel's r-loop has two staging forms (EASYDIST_TN256_STAGING: the
 three-buffer ring and the older issue-then-drain loop); both run under both
 maps, and two shapes give the ring a last slice shorter than its prefetch
-distance.
+distance.  The shapes with P or Q below 256 reach gemm_tn_kernel, the
+128-tile instantiation: with and without a split, with one r-tile and with
+several per slice, and with a second tile column that skips the column sum.
 """
 import pytest
 import torch
@@ -35,6 +38,11 @@ CASES = [
     (1024, 256, 128),   # 128-tile kernel with its power-of-two split
     (2336, 768, 256),   # 73 r-tiles, 9 slices of 9: the last holds 1 tile
     (2080, 256, 512),   # 65 r-tiles, 8 slices of 9: the last holds 2 tiles
+    # the 128-tile instantiation's remaining paths
+    (32, 128, 128),     # one r-tile, no split: direct stores, empty loop tail
+    (96, 128, 256),     # 3 r-tiles, no split, 2 tiles: buffers wrap, q0 != 0
+    (512, 128, 384),    # 3 tiles x 16 slices of one r-tile
+    (4096, 256, 128),   # R fits the 256 kernel but Q < 256: 8 r-tiles a slice
 ]
 
 
