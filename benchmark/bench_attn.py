@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Flash attention kernel timing: fwd, dq and dkv, causal and not, under
-both workgroup maps (EASYDIST_ATTN_MAP, read by the launch code at every
-call so one process can alternate them).
+both workgroup maps (EASYDIST_ATTN_MAP) and both LDS forms
+(EASYDIST_ATTN_TR: 1 = one image per tile read transposed, 0 = the second
+transposed copy); the launch code reads both at every call, so one process
+can alternate them.
 
 Event timings give fwd and total bwd (delta + dq + dkv).  Per-kernel
 figures for dq and dkv come from a kernel trace: either run this script
@@ -9,9 +11,10 @@ under `rocprofv3 --kernel-trace --stats` with one --map and one --causal
 value, in a run of its own, or pass --per-kernel to collect them with the
 torch profiler in-process (attributed per configuration).
 
-Every configuration is timed --repeats times, the maps alternated inside
-each repeat, and min / median / max are reported so a difference can be
-set against the run-to-run spread.  One JSON line per configuration.
+Every configuration is timed --repeats times, the maps and forms
+alternated inside each repeat, and min / median / max are reported so a
+difference can be set against the run-to-run spread.  One JSON line per
+configuration.
 """
 import argparse
 import json
@@ -79,6 +82,10 @@ def main():
     ap.add_argument("--map", choices=["0", "1", "both", "env"], default="env",
                     help="workgroup map: 0 legacy, 1 balanced, both = "
                          "alternate them, env = leave EASYDIST_ATTN_MAP alone")
+    ap.add_argument("--tr", choices=["0", "1", "both", "env"], default="env",
+                    help="LDS form: 0 transposed copy, 1 transposed reads, "
+                         "both = alternate them, env = leave EASYDIST_ATTN_TR "
+                         "alone (unset: each kernel's shipped default)")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warm-iters", type=int, default=50)
@@ -91,13 +98,18 @@ def main():
     ext = ops.load_extension()
     assert ext is not None
     causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
-    maps = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}[args.map]
+    pick = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}
+    # a configuration is a (map, tr) pair
+    maps = [(m, t) for m in pick[args.map] for t in pick[args.tr]]
     shapes = SHAPES if args.shapes == "all" else \
         [SHAPES[int(i)] for i in args.shapes.split(",")]
 
-    def set_map(m):
+    def set_map(cfg):
+        m, t = cfg
         if m is not None:
             os.environ["EASYDIST_ATTN_MAP"] = m
+        if t is not None:
+            os.environ["EASYDIST_ATTN_TR"] = t
 
     for (B, H, S, D) in shapes:
         q = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16)
@@ -119,7 +131,7 @@ def main():
                 time_ms(fwd, args.warm_iters, 0)
                 time_ms(bwd, args.warm_iters, 0)
             for _ in range(args.repeats):
-                for m in maps:          # alternate maps inside a repeat
+                for m in maps:          # alternate configs inside a repeat
                     set_map(m)
                     t_fwd[m].append(time_ms(fwd, args.iters))
                     t_bwd[m].append(time_ms(bwd, args.iters))
@@ -134,8 +146,10 @@ def main():
             fl_bwd = fl_fwd * 2.5       # model flops of the backward
             for m in maps:
                 r = {"shape": f"B{B} H{H} S{S} D{D}", "causal": int(causal),
-                     "map": m if m is not None
+                     "map": m[0] if m[0] is not None
                      else os.environ.get("EASYDIST_ATTN_MAP", "1"),
+                     "tr": m[1] if m[1] is not None
+                     else os.environ.get("EASYDIST_ATTN_TR", "default"),
                      "fwd_ms": stats(t_fwd[m]), "bwd_ms": stats(t_bwd[m])}
                 r["fwd_tf"] = fl_fwd / r["fwd_ms"]["med"] / 1e9
                 r["bwd_tf"] = fl_bwd / r["bwd_ms"]["med"] / 1e9

@@ -5,8 +5,9 @@
 // 128-row block (q rows in fwd/dq, keys in dkv) of one (batch, head),
 // placed on the chip by attn_block_map; each wave owns 16 rows.  The
 // 64-row tiles of the other operand pair are register-prefetched from
-// global memory and double-buffered in LDS under the lsw swizzle; every
-// product runs on v_mfma_f32_16x16x32_bf16.
+// global memory and double-buffered in LDS, one swizzled row-major image
+// per tile that is read by rows (ds_read_b128) and by columns
+// (ds_read_b64_tr_b16); every product runs on v_mfma_f32_16x16x32_bf16.
 //
 // fwd and dq compute the SWAPPED-operand S^T = K Q^T, so each lane holds
 // one q row: the online-softmax state (m, l) is one register pair per
@@ -19,6 +20,7 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <climits>
+#include <type_traits>
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using bf16x8v = __attribute__((ext_vector_type(8))) __bf16;
@@ -33,6 +35,86 @@ using bf16x8v = __attribute__((ext_vector_type(8))) __bf16;
 // (e ^= ((e>>7)&15)<<3) is an involution, keeps 8-element chunks whole,
 // and is injective across the 16 rows of a fragment for both row widths.
 DEVINL int lsw(int e) { return e ^ (((e >> 7) & 15) << 3); }
+
+// TR = 1: ONE row-major [rows][D] image per tile.  The products that sum
+// over the image's ROWS (PV, dS K, P^T dO, dS^T Q) take their B operand
+// from it with the gfx950 transposed read (tr_frag) instead of from a
+// second, transposed copy built with 2-byte scalar stores.  lsw leaves
+// that read 2-way conflicted at both row widths: a 32-lane half takes
+// rows r..r+3 and r+8..r+11 in the two 16-B chunks {2j, 2j+1}, and lsw
+// sends (row, chunk 2j+1) and (row+1, chunk 2j) to one slot.  tsw XORs
+// only row bits 0, 1 and 3 into chunk bits 3, 1 and 2 (row bit 0 is
+// already bit 3 of the 256-B slot index at D = 64, hence the mask) and
+// leaves chunk bit 0 alone: by the bank rule ((byte/4) % 64, groups as in
+// the LDS table) the ds_read_b128 row read, the transposed read and the
+// 16-B store are all conflict-free at D = 64 and D = 128.  Element-index
+// form like lsw; 8-element chunks stay whole.  Stores and both kinds of
+// read go through isw.
+template <int D>
+DEVINL int tsw(int e) {
+  const int r = e / D;
+  const int g = (((r & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 1) & 1) << 1))
+                & (D / 8 - 1);
+  return e ^ (g << 3);
+}
+template <int D, bool TR>
+DEVINL int isw(int e) {
+  if constexpr (TR) return tsw<D>(e);
+  else return lsw(e);
+}
+
+// B-operand fragment of v_mfma_f32_16x16x32_bf16 from a row-major tsw
+// image: n = image column c0 + fr, k = image rows r0 + 8*fg + 0..7, with
+// r0 a multiple of 32 and c0 of 16.  Two ds_read_b64_tr_b16, rows +0..3
+// and +4..7: lane 4q+p of a 16-lane group supplies the address of row q,
+// columns 4p..4p+3, and lane i receives column i.  A lane's row is
+// r0 + 8*fg + 4h + q, so the row bits tsw uses (0, 1, 3) are the lane's
+// own for every fragment: tr_lane() gives the lane's element offset and
+// XOR once, and a fragment costs one xor-add per c0 with r0 and h in the
+// instruction's immediate offset.  Needs EXEC all ones: call it under
+// wave-uniform control flow only.
+using v4s = __attribute__((ext_vector_type(4))) short;
+using v8s = __attribute__((ext_vector_type(8))) short;
+struct TrLane { int off, x; };
+template <int D, bool TR>
+DEVINL TrLane tr_lane(int fr, int fg) {
+  if constexpr (!TR) return {0, 0};
+  const int e = (fg * 8 + (fr >> 2)) * D + (fr & 3) * 4;
+  return {e, tsw<D>(e) ^ e};
+}
+template <int D>
+DEVINL bf16x8v tr_frag(const bf16* img, TrLane tl, int r0, int c0) {
+  // tl.x has bits 4..6 only (tsw leaves chunk bit 0 alone) and c0 bits
+  // 4..6 only, so the XOR stays clear of the lane's (fr & 3) * 4
+  const bf16* a = img + ((c0 ^ tl.x) + tl.off) + r0 * D;
+  v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) v4s*)a);
+  v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) v4s*)(a + 4 * D));
+  v8s out = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8v, out);
+}
+
+// Register type of one staged 16-byte vector.  The struct (element access
+// for the 2-byte transposed stores) reaches LDS through a stack slot; TR
+// never takes a vector apart, and the plain vector type keeps the
+// prefetch in registers (no scratch in any TR = 1 kernel).
+template <bool TR>
+using stage_t = std::conditional_t<TR, bf16x8v, bf16x8>;
+
+// LDS elements (bf16) each kernel asks for; the launch code sizes the
+// dynamic LDS from these.  TR = 0 keeps the parent's sizes, including the
+// 8 * 16 * KB strip elements fwd and dq no longer touch (LDS size sets
+// workgroups per CU, so TR = 0 stays what was measured before).
+template <int D, bool TR> constexpr int fwd_lds_elems() {
+  return 2 * (2 * KB * D) + (TR ? 0 : 8 * 16 * KB);
+}
+template <int D, bool TR> constexpr int dq_lds_elems() {
+  return 2 * ((TR ? 2 : 3) * KB * D) + (TR ? 0 : 8 * 16 * KB);
+}
+template <int D, bool TR> constexpr int dkv_lds_elems() {
+  return 2 * ((TR ? 2 : 4) * QB * D) + 8 * 16 * QB;   // + P^T/dS^T strips
+}
 
 
 // ---- shared pieces of the swapped-operand (S^T) form ----------------------
@@ -82,7 +164,7 @@ DEVINL bf16x8v swp_butterfly(const unsigned pk[][2], int ks, int fg) {
 // butterfly above instead of an LDS strip round-trip.  The un-swapped
 // strip form, a 256-row (two fragments per wave) block and direct-from-L2
 // K reads were all A/B'd on hardware and lost (profiles/README.md).
-template <int D>
+template <int D, bool TR>
 __global__ void
 __launch_bounds__(512, (D == 64 ? 4 : 1))  // waves/SIMD floor
 flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
@@ -114,15 +196,18 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
   const int lane = threadIdx.x % WAVE;
   const int wave = threadIdx.x / WAVE;
 
-  // LDS: DOUBLE-BUFFERED K [KB][D] + V^T [D][KB] (lsw) pairs.
+  // LDS: DOUBLE-BUFFERED K [KB][D] + V^T [D][KB] (lsw) pairs; under TR
+  // the second tile is V [KB][D] and both are tsw images.
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TILE_K = KB * D;
   constexpr int TILE_VT = KB * D;   // [D][KB] linear + lsw swizzle
+  static_assert(2 * (TILE_K + TILE_VT) <= fwd_lds_elems<D, TR>());
   bf16* smem_b = reinterpret_cast<bf16*>(smem);
   constexpr int NTHR = 8 * WAVE;   // 512
 
   const int fr = lane & 15;        // fragment row/col index
   const int fg = lane >> 4;        // fragment k-group (8 contiguous)
+  const TrLane trl = tr_lane<D, TR>(fr, fg);   // transposed reads (TR only)
 
   const int qr0 = qb0 + wave * 16; // this wave's first q row
   const int qrow = qr0 + fr;       // this lane's q row
@@ -155,15 +240,17 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
   const int kv_end = causal ? min(S, qb0 + QBLK) : S;
   const int n_tiles = (kv_end + KB - 1) / KB;
   constexpr int PF = TILE_K / (NTHR * 8);    // 16B vectors per thread
-  bf16x8 kreg[PF], vreg[PF];
+  stage_t<TR> kreg[PF], vreg[PF];
 
   auto load_tile = [&](int t) {
     #pragma unroll
     for (int pi = 0; pi < PF; ++pi) {
       const int e = threadIdx.x * 8 + pi * (NTHR * 8);
       const int row = t * KB + e / D, col = e % D;
-      kreg[pi] = *reinterpret_cast<const bf16x8*>(&k[(long)row * kss + col]);
-      vreg[pi] = *reinterpret_cast<const bf16x8*>(&v[(long)row * vss + col]);
+      kreg[pi] = *reinterpret_cast<const stage_t<TR>*>(
+          &k[(long)row * kss + col]);
+      vreg[pi] = *reinterpret_cast<const stage_t<TR>*>(
+          &v[(long)row * vss + col]);
     }
   };
   auto store_tile = [&](int t) {
@@ -172,11 +259,15 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
     #pragma unroll
     for (int pi = 0; pi < PF; ++pi) {
       const int e = threadIdx.x * 8 + pi * (NTHR * 8);
-      *reinterpret_cast<bf16x8*>(&kb[lsw(e)]) = kreg[pi];
-      const int row = e / D, col = e % D;
-      #pragma unroll
-      for (int i = 0; i < 8; ++i)
-        vb[lsw((col + i) * KB + row)] = vreg[pi].v[i];
+      *reinterpret_cast<stage_t<TR>*>(&kb[isw<D, TR>(e)]) = kreg[pi];
+      if constexpr (TR) {
+        *reinterpret_cast<bf16x8v*>(&vb[tsw<D>(e)]) = vreg[pi];
+      } else {
+        const int row = e / D, col = e % D;
+        #pragma unroll
+        for (int i = 0; i < 8; ++i)
+          vb[lsw((col + i) * KB + row)] = vreg[pi].v[i];
+      }
     }
   };
 
@@ -205,7 +296,7 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
         #pragma unroll
         for (int ks = 0; ks < D / 32; ++ks) {
           bf16x8v kf = *reinterpret_cast<const bf16x8v*>(
-              &k_lds[lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+              &k_lds[isw<D, TR>((j * 16 + fr) * D + ks * 32 + fg * 8)]);
           s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               kf, qf[ks], s_acc[j], 0, 0, 0);
         }
@@ -267,8 +358,12 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
         bf16x8v pv = swp_butterfly(pk, ks, fg);
         #pragma unroll
         for (int j = 0; j < D / 16; ++j) {
-          bf16x8v vf = *reinterpret_cast<const bf16x8v*>(
-              &vt_lds[lsw((j * 16 + fr) * KB + ks * 32 + fg * 8)]);
+          bf16x8v vf;
+          if constexpr (TR)
+            vf = tr_frag<D>(vt_lds, trl, ks * 32, j * 16);
+          else
+            vf = *reinterpret_cast<const bf16x8v*>(
+                &vt_lds[lsw((j * 16 + fr) * KB + ks * 32 + fg * 8)]);
           o_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               pv, vf, o_acc[j], 0, 0, 0);
         }
@@ -312,6 +407,21 @@ static inline int ed_attn_map_mode() {
   return (e && atoi(e) == 0) ? ATTN_MAP_LEGACY : ATTN_MAP_BALANCED;
 }
 
+// EASYDIST_ATTN_TR: 1 = one LDS image per tile, read transposed by the
+// hardware; 0 = the second, transposed copy, kept for A/B timing and the
+// bit-equality test.  Unset, each kernel runs the form that measured
+// faster (profiles/README.md Round 6): TR = 1 everywhere but the D = 64
+// dkv kernel, which stays VGPR-bound at one workgroup per CU under either
+// form and ran 0.3% (causal) to 6.8% (full) slower with the transposed
+// reads.  Read at every launch like the map.
+#define ATTN_TR_FWD 1
+#define ATTN_TR_DQ 1
+#define ATTN_TR_DKV(D) ((D) == 128)
+static inline bool ed_attn_tr(bool dflt) {
+  const char* e = getenv("EASYDIST_ATTN_TR");
+  return e ? atoi(e) != 0 : dflt;
+}
+
 // 1-D grid of nblk * nbh workgroups: the linear id the map consumes
 static inline dim3 ed_attn_grid(long nblk, long nbh, const char* who) {
   TORCH_CHECK(nblk * nbh <= (long)INT_MAX, who,
@@ -336,12 +446,17 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
   dim3 grid = ed_attn_grid((S + 2 * QB - 1) / (2 * QB), (long)B * H,
                            "flash_attn_fwd"), block(512);
   const int map_mode = ed_attn_map_mode();
-  // the trailing 8 * 16 * KB strip elements are unused since the strip
-  // form left; LDS size sets workgroups per CU, so reclaiming them needs a
-  // measured change
-  size_t lds = (2 * ((size_t)KB * D + (size_t)KB * D) + 8 * 16 * KB) * 2;
+  // LDS bytes -> workgroups per 160-KiB CU, D = 64 / 128:
+  //   TR = 0: 48 / 80 KiB -> 3 / 2;  TR = 1: 32 / 64 KiB -> 5 / 2
+  const bool tr = ed_attn_tr(ATTN_TR_FWD);
+  size_t lds = sizeof(bf16) *
+      (D == 64 ? (tr ? fwd_lds_elems<64, true>() : fwd_lds_elems<64, false>())
+               : (tr ? fwd_lds_elems<128, true>()
+                     : fwd_lds_elems<128, false>()));
   float scale = 1.f / sqrtf((float)D);
-  auto kern = (D == 64) ? flash_fwd_kernel<64> : flash_fwd_kernel<128>;
+  auto kern = (D == 64)
+      ? (tr ? flash_fwd_kernel<64, true> : flash_fwd_kernel<64, false>)
+      : (tr ? flash_fwd_kernel<128, true> : flash_fwd_kernel<128, false>);
   hipLaunchKernelGGL(kern, grid, block, lds, stream,
       (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
       (const bf16*)v.data_ptr(), (bf16*)out.data_ptr(),
@@ -365,7 +480,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
 // hold row fr, k-slice fg; C/D lanes hold row 4*fg+r, col fr.
 // ---------------------------------------------------------------------------
 
-template <int D>
+template <int D, bool TR>
 __global__ void __launch_bounds__(512)
 flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -399,16 +514,19 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   const int qr0 = qb0 + wave * 16;
   const int fr = lane & 15;
   const int fg = lane >> 4;
+  const TrLane trl = tr_lane<D, TR>(fr, fg);   // transposed reads (TR only)
 
-  // DOUBLE-BUFFERED K/V/K^T tiles (3 tiles per buffer): the single-
+  // DOUBLE-BUFFERED K/V/K^T tiles (3 tiles per buffer; under TR K and V
+  // only, dS K reads the K image transposed): the single-
   // buffered store->barrier->compute form serialized the full staging
   // latency into every tile (bwd ran at ~127 TF vs the double-buffered
   // forward's 158+)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int DQBUF = 3 * KB * D;                // elements per buffer
+  constexpr int DQBUF = (TR ? 2 : 3) * KB * D;     // elements per buffer
+  static_assert(2 * DQBUF <= dq_lds_elems<D, TR>());
   bf16* k_lds = reinterpret_cast<bf16*>(smem);     // + buf * DQBUF
   bf16* v_lds = k_lds + KB * D;
-  bf16* kt_lds = v_lds + KB * D;                   // K^T [D][KB] + lsw
+  bf16* kt_lds = v_lds + KB * D;       // K^T [D][KB] + lsw (TR = 0 only)
 
   // A-operand fragments for this wave's 16 q rows
   bf16x8v qf[D / 32], dof[D / 32];
@@ -433,7 +551,7 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   // MFMA/softmax work on kv0 runs (the unprefetched form exposed the
   // full HBM latency behind two barriers every tile)
   constexpr int NV = KB * D / (512 * 8);
-  bf16x8 kreg[NV], vreg[NV];
+  stage_t<TR> kreg[NV], vreg[NV];
   auto kv_load = [&](int t0) {
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
@@ -441,20 +559,24 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       // row strides: the inputs may be [B,S,H,D]-layout views
       const long row = t0 + e / D;
       const int col = e % D;
-      kreg[pi] = *reinterpret_cast<const bf16x8*>(&k[row * kss + col]);
-      vreg[pi] = *reinterpret_cast<const bf16x8*>(&v[row * vss + col]);
+      kreg[pi] = *reinterpret_cast<const stage_t<TR>*>(&k[row * kss + col]);
+      vreg[pi] = *reinterpret_cast<const stage_t<TR>*>(&v[row * vss + col]);
     }
   };
   auto kv_store = [&](int buf) {
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
       const int e = threadIdx.x * 8 + pi * 4096;
-      *reinterpret_cast<bf16x8*>(&k_lds[buf * DQBUF + lsw(e)]) = kreg[pi];
-      *reinterpret_cast<bf16x8*>(&v_lds[buf * DQBUF + lsw(e)]) = vreg[pi];
-      const int row = e / D, col = e % D;
-      #pragma unroll
-      for (int i = 0; i < 8; ++i)
-        kt_lds[buf * DQBUF + lsw((col + i) * KB + row)] = kreg[pi].v[i];
+      *reinterpret_cast<stage_t<TR>*>(
+          &k_lds[buf * DQBUF + isw<D, TR>(e)]) = kreg[pi];
+      *reinterpret_cast<stage_t<TR>*>(
+          &v_lds[buf * DQBUF + isw<D, TR>(e)]) = vreg[pi];
+      if constexpr (!TR) {
+        const int row = e / D, col = e % D;
+        #pragma unroll
+        for (int i = 0; i < 8; ++i)
+          kt_lds[buf * DQBUF + lsw((col + i) * KB + row)] = kreg[pi].v[i];
+      }
     }
   };
   kv_load(0);
@@ -481,9 +603,9 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       #pragma unroll
       for (int ks = 0; ks < D / 32; ++ks) {
         bf16x8v kf = *reinterpret_cast<const bf16x8v*>(
-            &k_lds[bofs + lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+            &k_lds[bofs + isw<D, TR>((j * 16 + fr) * D + ks * 32 + fg * 8)]);
         bf16x8v vf = *reinterpret_cast<const bf16x8v*>(
-            &v_lds[bofs + lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+            &v_lds[bofs + isw<D, TR>((j * 16 + fr) * D + ks * 32 + fg * 8)]);
         s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             kf, qf[ks], s_acc[j], 0, 0, 0);
         dp_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -510,13 +632,18 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     #pragma unroll
     for (int ks = 0; ks < KB / 32; ++ks)
       dsf[ks] = swp_butterfly(pk, ks, fg);
-    // dq += dS @ K: B-operand from K^T — contiguous vector loads
+    // dq += dS @ K: B-operand from K^T — contiguous vector loads — or,
+    // under TR, from the K image by transposed reads
     #pragma unroll
     for (int j = 0; j < D / 16; ++j) {
       #pragma unroll
       for (int ks = 0; ks < KB / 32; ++ks) {
-        bf16x8v kcol = *reinterpret_cast<const bf16x8v*>(
-            &kt_lds[bofs + lsw((j * 16 + fr) * KB + ks * 32 + fg * 8)]);
+        bf16x8v kcol;
+        if constexpr (TR)
+          kcol = tr_frag<D>(k_lds + bofs, trl, ks * 32, j * 16);
+        else
+          kcol = *reinterpret_cast<const bf16x8v*>(
+              &kt_lds[bofs + lsw((j * 16 + fr) * KB + ks * 32 + fg * 8)]);
         dq_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsf[ks], kcol,
                                                             dq_acc[j], 0, 0,
                                                             0);
@@ -535,7 +662,7 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   }
 }
 
-template <int D, int SW = 0>
+template <int D, int SW, bool TR>
 __global__ void __launch_bounds__(512)
 flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -569,14 +696,17 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   const int kr0 = kb0 + wave * 16;          // this wave's first key row
   const int fr = lane & 15;
   const int fg = lane >> 4;
+  const TrLane trl = tr_lane<D, TR>(fr, fg);   // transposed reads (TR only)
 
-  // DOUBLE-BUFFERED Q/dO/Q^T/dO^T tiles (see dq note)
+  // DOUBLE-BUFFERED Q/dO/Q^T/dO^T tiles (see dq note); under TR Q and dO
+  // only, P^T dO and dS^T Q read those images transposed
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int KVBUF = 4 * QB * D;                // elements per buffer
+  constexpr int KVBUF = (TR ? 2 : 4) * QB * D;     // elements per buffer
+  static_assert(2 * KVBUF + 8 * 16 * QB == dkv_lds_elems<D, TR>());
   bf16* q_lds = reinterpret_cast<bf16*>(smem);     // + buf * KVBUF
   bf16* do_lds = q_lds + QB * D;
-  bf16* qt_lds = do_lds + QB * D;                  // Q^T [D][QB] + lsw
-  bf16* dot_lds = qt_lds + QB * D;                 // dO^T [D][QB] + lsw
+  bf16* qt_lds = do_lds + QB * D;      // Q^T [D][QB] + lsw (TR = 0 only)
+  bf16* dot_lds = qt_lds + QB * D;     // dO^T [D][QB] + lsw (TR = 0 only)
   bf16* s_lds = reinterpret_cast<bf16*>(smem) + 2 * KVBUF + wave * 16 * QB;
 
   bf16x8v kf[D / 32], vf[D / 32];
@@ -598,7 +728,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   const int q_start = causal ? kb0 : 0;
   // register-staged Q/dO prefetch (see dq kernel note)
   constexpr int NV = QB * D / (512 * 8);
-  bf16x8 qreg[NV], dreg[NV];
+  stage_t<TR> qreg[NV], dreg[NV];
   auto q_load = [&](int t0) {
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
@@ -606,21 +736,26 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       // row strides: the inputs may be [B,S,H,D]-layout views
       const long row = t0 + e / D;
       const int col = e % D;
-      qreg[pi] = *reinterpret_cast<const bf16x8*>(&q[row * qss + col]);
-      dreg[pi] = *reinterpret_cast<const bf16x8*>(&dO_[row * dss + col]);
+      qreg[pi] = *reinterpret_cast<const stage_t<TR>*>(&q[row * qss + col]);
+      dreg[pi] = *reinterpret_cast<const stage_t<TR>*>(
+          &dO_[row * dss + col]);
     }
   };
   auto q_store = [&](int buf) {
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
       const int e = threadIdx.x * 8 + pi * 4096;
-      *reinterpret_cast<bf16x8*>(&q_lds[buf * KVBUF + lsw(e)]) = qreg[pi];
-      *reinterpret_cast<bf16x8*>(&do_lds[buf * KVBUF + lsw(e)]) = dreg[pi];
-      const int row = e / D, col = e % D;
-      #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        qt_lds[buf * KVBUF + lsw((col + i) * QB + row)] = qreg[pi].v[i];
-        dot_lds[buf * KVBUF + lsw((col + i) * QB + row)] = dreg[pi].v[i];
+      *reinterpret_cast<stage_t<TR>*>(
+          &q_lds[buf * KVBUF + isw<D, TR>(e)]) = qreg[pi];
+      *reinterpret_cast<stage_t<TR>*>(
+          &do_lds[buf * KVBUF + isw<D, TR>(e)]) = dreg[pi];
+      if constexpr (!TR) {
+        const int row = e / D, col = e % D;
+        #pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          qt_lds[buf * KVBUF + lsw((col + i) * QB + row)] = qreg[pi].v[i];
+          dot_lds[buf * KVBUF + lsw((col + i) * QB + row)] = dreg[pi].v[i];
+        }
       }
     }
   };
@@ -650,9 +785,9 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       #pragma unroll
       for (int ks = 0; ks < D / 32; ++ks) {
         bf16x8v qfb = *reinterpret_cast<const bf16x8v*>(
-            &q_lds[bofs + lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+            &q_lds[bofs + isw<D, TR>((j * 16 + fr) * D + ks * 32 + fg * 8)]);
         bf16x8v dob = *reinterpret_cast<const bf16x8v*>(
-            &do_lds[bofs + lsw((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+            &do_lds[bofs + isw<D, TR>((j * 16 + fr) * D + ks * 32 + fg * 8)]);
         if (SW) {
           st_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               qfb, kf[ks], st_acc[j], 0, 0, 0);
@@ -729,13 +864,18 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       ptf[ks] = *reinterpret_cast<const bf16x8v*>(
           &s_lds[lsw(fr * QB + ks * 32 + fg * 8)]);
     }
-    // dV += P^T @ dO: B-operand from dO^T — contiguous vector loads
+    // dV += P^T @ dO: B-operand from dO^T — contiguous vector loads — or,
+    // under TR, from the dO image by transposed reads
     #pragma unroll
     for (int j = 0; j < D / 16; ++j) {
       #pragma unroll
       for (int ks = 0; ks < QB / 32; ++ks) {
-        bf16x8v docol = *reinterpret_cast<const bf16x8v*>(
-            &dot_lds[bofs + lsw((j * 16 + fr) * QB + ks * 32 + fg * 8)]);
+        bf16x8v docol;
+        if constexpr (TR)
+          docol = tr_frag<D>(do_lds + bofs, trl, ks * 32, j * 16);
+        else
+          docol = *reinterpret_cast<const bf16x8v*>(
+              &dot_lds[bofs + lsw((j * 16 + fr) * QB + ks * 32 + fg * 8)]);
         dv_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ptf[ks], docol,
                                                             dv_acc[j], 0, 0,
                                                             0);
@@ -777,13 +917,18 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       dstf[ks] = *reinterpret_cast<const bf16x8v*>(
           &s_lds[lsw(fr * QB + ks * 32 + fg * 8)]);
     }
-    // dK += dS^T @ Q: B-operand from Q^T — contiguous vector loads
+    // dK += dS^T @ Q: B-operand from Q^T — contiguous vector loads — or,
+    // under TR, from the Q image by transposed reads
     #pragma unroll
     for (int j = 0; j < D / 16; ++j) {
       #pragma unroll
       for (int ks = 0; ks < QB / 32; ++ks) {
-        bf16x8v qcolf = *reinterpret_cast<const bf16x8v*>(
-            &qt_lds[bofs + lsw((j * 16 + fr) * QB + ks * 32 + fg * 8)]);
+        bf16x8v qcolf;
+        if constexpr (TR)
+          qcolf = tr_frag<D>(q_lds + bofs, trl, ks * 32, j * 16);
+        else
+          qcolf = *reinterpret_cast<const bf16x8v*>(
+              &qt_lds[bofs + lsw((j * 16 + fr) * QB + ks * 32 + fg * 8)]);
         dk_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dstf[ks], qcolf,
                                                             dk_acc[j], 0, 0,
                                                             0);
@@ -864,21 +1009,39 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   dim3 grid = ed_attn_grid(S / (2 * QB), (long)B * H, "flash_attn_bwd"),
        block(512);
   const int map_mode = ed_attn_map_mode();
-  // dq: DOUBLE-buffered (K+V+K^T) tiles.  The trailing 8 * 16 * KB strip
-  // elements are unused since the strip form left; LDS size sets workgroups
-  // per CU, so reclaiming them needs a measured change
-  size_t lds = (2 * (3 * (size_t)KB * D) + 8 * 16 * KB) * 2;
-  // dkv: DOUBLE-buffered (Q+dO+Q^T+dO^T) tiles + wave strips
-  size_t lds_kv = (2 * (4 * (size_t)QB * D) + 8 * 16 * QB) * 2;
+  // LDS bytes -> workgroups per 160-KiB CU, D = 64 / 128:
+  //   dq  (K+V+K^T, or K+V under TR), double-buffered:
+  //     TR = 0: 64 / 112 KiB -> 2 / 1;  TR = 1: 32 / 64 KiB -> 5 / 2
+  //   dkv (Q+dO+Q^T+dO^T, or Q+dO under TR), double-buffered, + strips:
+  //     TR = 0: 80 / 144 KiB -> 2 / 1;  TR = 1: 48 / 80 KiB -> 3 / 2
+  const bool tr_q = ed_attn_tr(ATTN_TR_DQ), tr_kv = ed_attn_tr(ATTN_TR_DKV(D));
+  size_t lds = sizeof(bf16) *
+      (D == 64 ? (tr_q ? dq_lds_elems<64, true>() : dq_lds_elems<64, false>())
+               : (tr_q ? dq_lds_elems<128, true>()
+                       : dq_lds_elems<128, false>()));
+  size_t lds_kv = sizeof(bf16) *
+      (D == 64 ? (tr_kv ? dkv_lds_elems<64, true>()
+                        : dkv_lds_elems<64, false>())
+               : (tr_kv ? dkv_lds_elems<128, true>()
+                        : dkv_lds_elems<128, false>()));
   float scale = 1.f / sqrtf((float)D);
-  auto qkern = (D == 64) ? flash_bwd_dq_kernel<64> : flash_bwd_dq_kernel<128>;
+  auto qkern = (D == 64)
+      ? (tr_q ? flash_bwd_dq_kernel<64, true> : flash_bwd_dq_kernel<64, false>)
+      : (tr_q ? flash_bwd_dq_kernel<128, true>
+              : flash_bwd_dq_kernel<128, false>);
   static int swkv = []() {  // dkv butterfly measured SLOWER than the
     const char* e = getenv("EASYDIST_DKV_SWAP");   // strip (2.11 vs 1.74
     return e ? atoi(e) : 0;                        // ms) — default off
   }();
   auto kkern = (D == 64)
-      ? (swkv ? flash_bwd_dkv_kernel<64, 1> : flash_bwd_dkv_kernel<64>)
-      : (swkv ? flash_bwd_dkv_kernel<128, 1> : flash_bwd_dkv_kernel<128>);
+      ? (swkv ? (tr_kv ? flash_bwd_dkv_kernel<64, 1, true>
+                       : flash_bwd_dkv_kernel<64, 1, false>)
+              : (tr_kv ? flash_bwd_dkv_kernel<64, 0, true>
+                       : flash_bwd_dkv_kernel<64, 0, false>))
+      : (swkv ? (tr_kv ? flash_bwd_dkv_kernel<128, 1, true>
+                       : flash_bwd_dkv_kernel<128, 1, false>)
+              : (tr_kv ? flash_bwd_dkv_kernel<128, 0, true>
+                       : flash_bwd_dkv_kernel<128, 0, false>));
   hipLaunchKernelGGL(qkern, grid, block, lds, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
