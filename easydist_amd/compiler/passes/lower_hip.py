@@ -116,6 +116,124 @@ def lower_layer_norm(gm: fx.GraphModule) -> int:
     return n_lowered
 
 
+def _sig(n):
+    """(dtype, shape) of a node's tensor, or None when unknown. The dx
+    getitem that lower_layer_norm creates carries no meta: it is the
+    kernel's raw output, shaped and typed like the backward's x."""
+    v = _val(n)
+    if isinstance(v, torch.Tensor):
+        return v.dtype, tuple(v.shape)
+    if isinstance(n, fx.Node) and n.op == "call_function" \
+            and n.target is operator.getitem and n.args[1] == 0 \
+            and n.args[0].target in (
+                torch.ops.easydist_amd.layer_norm_bwd.default,
+                torch.ops.easydist_amd.layer_norm_bwd_res.default):
+        return _sig(n.args[0].args[1])
+    return None
+
+
+def _plain_bf16_add(n) -> bool:
+    """aten.add.Tensor of two equally shaped bf16 tensors, no alpha."""
+    if not (n.op == "call_function" and n.target is aten.add.Tensor
+            and len(n.args) == 2 and not n.kwargs
+            and all(isinstance(a, fx.Node) for a in n.args)):
+        return False
+    so, sa, sb = _sig(n), _sig(n.args[0]), _sig(n.args[1])
+    return so is not None and so[0] == torch.bfloat16 and so == sa == sb
+
+
+def lower_norm_residual_fuse(gm: fx.GraphModule) -> int:
+    """Fold the residual-stream adds into the LayerNorm kernels.
+
+    Forward:   s = add(a, b); ln = layer_norm_fwd(s, w, b, eps)
+            -> s, out, mean, rstd = add_layer_norm_fwd(a, b, w, b, eps)
+               (every other user of s reads the fused op's first output)
+    Backward:  d = add(g, getitem(layer_norm_bwd(...), 0)), either operand
+               order, the dx feeding nothing else
+            -> d, dw, db = layer_norm_bwd_res(..., res=g, mask)
+
+    Both adds re-stream tensors the norm kernel already holds in registers;
+    the fused ops give bit-identical results. Run AFTER lower_layer_norm.
+    """
+    graph = gm.graph
+    ln_fwd = torch.ops.easydist_amd.layer_norm_fwd.default
+    ln_bwd = torch.ops.easydist_amd.layer_norm_bwd.default
+    add_ln_fwd = torch.ops.easydist_amd.add_layer_norm_fwd.default
+    ln_bwd_res = torch.ops.easydist_amd.layer_norm_bwd_res.default
+    n_fwd = n_bwd = 0
+
+    for n in list(graph.nodes):
+        if not _plain_bf16_add(n):
+            continue
+        ln = next((u for u in n.users if u.op == "call_function"
+                   and u.target is ln_fwd and u.args[0] is n), None)
+        if ln is None:
+            continue
+        with graph.inserting_before(n):
+            fused = graph.call_function(add_ln_fwd,
+                                        (n.args[0], n.args[1]) + ln.args[1:])
+            s = graph.call_function(operator.getitem, (fused, 0))
+        fused.meta = dict(ln.meta)
+        s.meta = dict(n.meta)
+        for u in list(ln.users):
+            assert u.op == "call_function" and u.target is operator.getitem
+            with graph.inserting_before(u):
+                item = graph.call_function(operator.getitem,
+                                           (fused, u.args[1] + 1))
+            item.meta = dict(u.meta)
+            u.replace_all_uses_with(item)
+            graph.erase_node(u)
+        graph.erase_node(ln)
+        n.replace_all_uses_with(s)
+        graph.erase_node(n)
+        n_fwd += 1
+
+    order = {node: i for i, node in enumerate(graph.nodes)}
+    for n in list(graph.nodes):
+        if not _plain_bf16_add(n):
+            continue
+        for g, dx in (n.args, n.args[::-1]):
+            bwd = dx.args[0] if dx.op == "call_function" \
+                and dx.target is operator.getitem and dx.args[1] == 0 \
+                else None
+            if bwd is None or bwd.op != "call_function" \
+                    or bwd.target is not ln_bwd or len(dx.users) != 1:
+                continue
+            # the fused node takes the backward's place, where the dw/db
+            # consumers expect it: g has to exist by then
+            if order[g] > order[bwd]:
+                continue
+            with graph.inserting_before(bwd):
+                fused = graph.call_function(
+                    ln_bwd_res, bwd.args[:5] + (g, bwd.args[5]))
+            fused.meta = dict(bwd.meta)
+            order[fused] = order[bwd]
+            for u in list(bwd.users):
+                assert u.op == "call_function" \
+                    and u.target is operator.getitem
+                with graph.inserting_before(u):
+                    item = graph.call_function(operator.getitem,
+                                               (fused, u.args[1]))
+                item.meta = dict(n.meta if u is dx else u.meta)
+                order[item] = order[u]
+                if u is dx:
+                    n.replace_all_uses_with(item)
+                    graph.erase_node(n)
+                else:
+                    u.replace_all_uses_with(item)
+                graph.erase_node(u)
+            graph.erase_node(bwd)
+            n_bwd += 1
+            break
+
+    if n_fwd or n_bwd:
+        graph.lint()
+        gm.recompile()
+        logger.info("lower_hip: fused %d residual adds into LayerNorm "
+                    "forwards, %d into backwards", n_fwd, n_bwd)
+    return n_fwd + n_bwd
+
+
 def _strip_t(n):
     """Return x if n is aten.t(x), else None."""
     if isinstance(n, fx.Node) and n.op == "call_function" \

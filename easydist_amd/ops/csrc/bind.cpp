@@ -8,6 +8,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor>
 layer_norm_bwd(const at::Tensor& grad, const at::Tensor& x,
                const at::Tensor& mean, const at::Tensor& rstd,
                const std::optional<at::Tensor>& w, std::vector<bool> mask);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+add_layer_norm_fwd(const at::Tensor& a, const at::Tensor& b,
+                   const std::optional<at::Tensor>& w,
+                   const std::optional<at::Tensor>& bias, double eps);
+std::tuple<at::Tensor, at::Tensor, at::Tensor>
+layer_norm_bwd_res(const at::Tensor& grad, const at::Tensor& x,
+                   const at::Tensor& mean, const at::Tensor& rstd,
+                   const std::optional<at::Tensor>& w,
+                   const std::optional<at::Tensor>& res,
+                   std::vector<bool> mask);
 std::tuple<at::Tensor, at::Tensor>
 rms_norm_fwd(const at::Tensor& x, const std::optional<at::Tensor>& w,
              double eps);
@@ -68,6 +78,16 @@ ln_bwd_wrap(const at::Tensor& grad, const at::Tensor& x,
   return layer_norm_bwd(grad, x, mean, rstd, w, m);
 }
 
+static std::tuple<at::Tensor, at::Tensor, at::Tensor>
+ln_bwd_res_wrap(const at::Tensor& grad, const at::Tensor& x,
+                const at::Tensor& mean, const at::Tensor& rstd,
+                const std::optional<at::Tensor>& w,
+                const std::optional<at::Tensor>& res,
+                std::vector<int64_t> mask) {
+  std::vector<bool> m(mask.begin(), mask.end());
+  return layer_norm_bwd_res(grad, x, mean, rstd, w, res, m);
+}
+
 static std::tuple<std::vector<at::Tensor>, std::vector<at::Tensor>,
                   std::vector<at::Tensor>, std::vector<at::Tensor>>
 adam_wrap(at::TensorList params, at::TensorList grads, at::TensorList exp_avgs,
@@ -91,6 +111,10 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
         "-> (Tensor, Tensor, Tensor)");
   m.def("layer_norm_bwd(Tensor grad, Tensor x, Tensor mean, Tensor rstd, "
         "Tensor? w, int[] mask) -> (Tensor, Tensor, Tensor)");
+  m.def("add_layer_norm_fwd(Tensor a, Tensor b, Tensor? w, Tensor? bias, "
+        "float eps) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("layer_norm_bwd_res(Tensor grad, Tensor x, Tensor mean, Tensor rstd, "
+        "Tensor? w, Tensor? res, int[] mask) -> (Tensor, Tensor, Tensor)");
   m.def("rms_norm_fwd(Tensor x, Tensor? w, float eps) -> (Tensor, Tensor)");
   m.def("rms_norm_bwd(Tensor grad, Tensor x, Tensor rstd, Tensor? w) "
         "-> (Tensor, Tensor)");
@@ -125,6 +149,8 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
 TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
   m.impl("layer_norm_fwd", layer_norm_fwd);
   m.impl("layer_norm_bwd", ln_bwd_wrap);
+  m.impl("add_layer_norm_fwd", add_layer_norm_fwd);
+  m.impl("layer_norm_bwd_res", ln_bwd_res_wrap);
   m.impl("rms_norm_fwd", rms_norm_fwd);
   m.impl("rms_norm_bwd", rms_norm_bwd);
   m.impl("ce_fwd", ce_fwd);

@@ -17,6 +17,13 @@ lib.define("layer_norm_fwd(Tensor x, Tensor? w, Tensor? b, float eps) "
            "-> (Tensor, Tensor, Tensor)")
 lib.define("layer_norm_bwd(Tensor grad, Tensor x, Tensor mean, Tensor rstd, "
            "Tensor? w, bool[3] mask) -> (Tensor, Tensor, Tensor)")
+# residual-fused forms (lower_norm_residual_fuse): s = a + b feeds the norm,
+# and the norm's dx leaves through dx + res
+lib.define("add_layer_norm_fwd(Tensor a, Tensor b, Tensor? w, Tensor? bias, "
+           "float eps) -> (Tensor, Tensor, Tensor, Tensor)")
+lib.define("layer_norm_bwd_res(Tensor grad, Tensor x, Tensor mean, "
+           "Tensor rstd, Tensor? w, Tensor? res, bool[3] mask) "
+           "-> (Tensor, Tensor, Tensor)")
 lib.define("ln_bwd_ref(Tensor grad, Tensor x, SymInt[] norm_shape, "
            "Tensor mean, Tensor rstd, Tensor? w, Tensor? b, bool[] mask) "
            "-> (Tensor, Tensor, Tensor)")
@@ -100,7 +107,53 @@ def _ln_bwd_cuda(grad, x, mean, rstd, w, mask):
     return _ln_bwd_aten(grad, x, mean, rstd, w, mask)
 
 
+def _add_ln_fwd_aten(a, b, w, bias, eps):
+    s = torch.ops.aten.add.Tensor(a, b)
+    return (s,) + tuple(_ln_fwd_aten(s, w, bias, eps))
+
+
+def _add_ln_fwd_cuda(a, b, w, bias, eps):
+    ext = load_extension()
+    if ext is not None and a.dtype in (torch.bfloat16, torch.float32) \
+            and a.dtype == b.dtype and a.shape == b.shape \
+            and a.shape[-1] % 8 == 0:
+        w = w.to(a.dtype).contiguous() if w is not None else None
+        bias = bias.to(a.dtype).contiguous() if bias is not None else None
+        return ext.add_layer_norm_fwd(a.contiguous(), b.contiguous(), w,
+                                      bias, eps)
+    s = torch.ops.aten.add.Tensor(a, b)
+    return (s,) + tuple(_ln_fwd_cuda(s, w, bias, eps))
+
+
+def _ln_bwd_res_aten(grad, x, mean, rstd, w, res, mask):
+    dx, dw, db = _ln_bwd_aten(grad, x, mean, rstd, w, mask)
+    if res is not None:
+        dx = torch.ops.aten.add.Tensor(dx, res)
+    return dx, dw, db
+
+
+def _ln_bwd_res_cuda(grad, x, mean, rstd, w, res, mask):
+    ext = load_extension()
+    if ext is not None and x.dtype == torch.bfloat16 \
+            and x.shape[-1] % 8 == 0 \
+            and (res is None or (res.dtype == x.dtype
+                                 and res.shape == x.shape)):
+        w2 = w.to(x.dtype).contiguous() if w is not None else None
+        return ext.layer_norm_bwd_res(
+            grad.to(x.dtype).contiguous(), x.contiguous(), mean.contiguous(),
+            rstd.contiguous(), w2,
+            res.contiguous() if res is not None else None, list(mask))
+    dx, dw, db = _ln_bwd_cuda(grad, x, mean, rstd, w, mask)
+    if res is not None:
+        dx = torch.ops.aten.add.Tensor(dx, res)
+    return dx, dw, db
+
+
 lib.impl("layer_norm_fwd", _ln_fwd_aten, "CPU")
+lib.impl("add_layer_norm_fwd", _add_ln_fwd_aten, "CPU")
+lib.impl("add_layer_norm_fwd", _add_ln_fwd_cuda, "CUDA")
+lib.impl("layer_norm_bwd_res", _ln_bwd_res_aten, "CPU")
+lib.impl("layer_norm_bwd_res", _ln_bwd_res_cuda, "CUDA")
 lib.impl("layer_norm_fwd", _ln_fwd_cuda, "CUDA")
 lib.impl("layer_norm_bwd", _ln_bwd_aten, "CPU")
 lib.impl("layer_norm_bwd", _ln_bwd_cuda, "CUDA")
@@ -118,6 +171,16 @@ def _ln_bwd_fake(grad, x, mean, rstd, w, mask):
     d = x.shape[-1]
     dw = x.new_empty((d,), dtype=w.dtype if w is not None else x.dtype)
     return torch.empty_like(x), dw, dw.clone()
+
+
+@torch.library.register_fake("easydist_amd::add_layer_norm_fwd")
+def _add_ln_fwd_fake(a, b, w, bias, eps):
+    return (torch.empty_like(a),) + tuple(_ln_fwd_fake(a, w, bias, eps))
+
+
+@torch.library.register_fake("easydist_amd::layer_norm_bwd_res")
+def _ln_bwd_res_fake(grad, x, mean, rstd, w, res, mask):
+    return _ln_bwd_fake(grad, x, mean, rstd, w, mask)
 
 
 def _rms_fwd_aten(x, w, eps):
