@@ -739,11 +739,12 @@ at::Tensor gemm_nt_act(const at::Tensor& a, const at::Tensor& bt,
   auto c = at::empty({M, N}, a.options());
   auto stream = at::cuda::getCurrentCUDAStream();
   const bf16* bias_p = bias ? (const bf16*)bias->data_ptr() : nullptr;
+  // modes 1 and 3 are plain forward activations: no aux
+  TORCH_CHECK(!(act == 2 || act >= 4) || aux,
+              "gemm_nt: activation modes 2/4/5/6 need aux");
   if (K % BK2 == 0 && M >= BM2 && N >= 128) {
     unsigned nwg = ((M + BM2 - 1) / BM2) * ((N + BN2 - 1) / BN2);
     bf16* aux_p = aux ? (bf16*)aux->data_ptr() : nullptr;
-    TORCH_CHECK(act == 0 || !(act >= 2) || aux_p,
-                "gemm_nt: activation modes 2/4/5/6 need aux");
     hipLaunchKernelGGL(gemm_nt_256, dim3(nwg), dim3(512), 2 * BUF_B, stream,
         (const bf16*)a.data_ptr(), (const bf16*)bt.data_ptr(),
         (bf16*)c.data_ptr(), bias_p, aux_p, (int)act, (int)M, (int)N,

@@ -16,6 +16,27 @@ from typing import Callable, Dict, Set
 import torch
 
 
+_profiler_warm = False
+
+
+def _warm_profiler(activities) -> None:
+    """Open and close one throwaway session before the first real one.
+
+    The first profiler session of a process sets the device tracer up
+    (seconds), and the first kernel launched inside it can be stamped
+    before the session's start and dropped from the results: observed as
+    a map that held the side-stream kernels of a traced call but not the
+    kernel launched first, on the first session only, never on a later
+    one."""
+    global _profiler_warm
+    if _profiler_warm:
+        return
+    with torch.profiler.profile(activities=activities):
+        torch.zeros(1, device="cuda")
+        torch.cuda.synchronize()
+    _profiler_warm = True
+
+
 def trace_kernel_streams(fn: Callable, *args,
                          **kwargs) -> Dict[str, Set[int]]:
     """Run ``fn`` under the profiler; return {op_name: {stream ids}} for
@@ -26,6 +47,7 @@ def trace_kernel_streams(fn: Callable, *args,
     activities = [torch.profiler.ProfilerActivity.CPU]
     if torch.cuda.is_available():
         activities.append(torch.profiler.ProfilerActivity.CUDA)
+        _warm_profiler(activities)
     with torch.profiler.profile(activities=activities) as prof:
         fn(*args, **kwargs)
         if torch.cuda.is_available():
