@@ -15,6 +15,9 @@ Every configuration is timed --repeats times, the maps and forms
 alternated inside each repeat, and min / median / max are reported so a
 difference can be set against the run-to-run spread.  One JSON line per
 configuration.
+
+--ragged times a shape set of its own instead (S % 128 != 0, see
+run_ragged); without it the output is what it always was.
 """
 import argparse
 import json
@@ -30,6 +33,11 @@ import easydist_amd.ops as ops
 
 SHAPES = [(64, 12, 1024, 64), (16, 16, 2048, 128),
           (64, 12, 1152, 64)]   # nblk = 9: legacy map is naturally mixed
+
+# --ragged only (never part of "all" above): ((B, H, S, D), causal) with
+# S % 128 != 0; EASYDIST_ATTN_TR does not apply to these
+RAGGED_SHAPES = [((256, 16, 197, 64), False),    # ViT-Large
+                 ((64, 12, 1000, 64), True)]
 
 # report name -> substring of the kernel's name in a trace
 KERNELS = {"fwd": "flash_fwd", "dq": "flash_bwd_dq", "dkv": "flash_bwd_dkv",
@@ -76,8 +84,60 @@ def stats(xs):
             "all": [round(x, 4) for x in xs]}   # in measurement order
 
 
+def run_ragged(args):
+    """--ragged: the public op, forward + backward, at each ragged shape
+    and at the next S that is a multiple of 128, alternated inside each
+    repeat.  The public op, not the extension, so the same script also
+    times a build whose kernels refuse these shapes (aten math path).
+    peak_mib: peak allocated memory of one forward + backward above what
+    the inputs hold."""
+    from easydist_amd.ops.attention import scaled_dot_product_attention
+    picked = RAGGED_SHAPES if args.shapes == "all" else \
+        [RAGGED_SHAPES[int(i)] for i in args.shapes.split(",")]
+    for (B, H, S, D), causal in picked:
+        S_al = (S + 127) // 128 * 128
+        cfgs = {}
+        for s in (S, S_al):
+            q, k, v = (torch.randn(B, H, s, D, device="cuda",
+                                   dtype=torch.bfloat16, requires_grad=True)
+                       for _ in range(3))
+            g = torch.randn(B, H, s, D, device="cuda", dtype=torch.bfloat16)
+
+            def step(q=q, k=k, v=v, g=g):
+                scaled_dot_product_attention(q, k, v, causal=causal) \
+                    .backward(g)
+                q.grad = k.grad = v.grad = None
+            cfgs[s] = step
+        times = {s: [] for s in cfgs}
+        peak = {}
+        for s, step in cfgs.items():
+            time_ms(step, args.warm_iters, 0)
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            step()
+            torch.cuda.synchronize()
+            peak[s] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+        for _ in range(args.repeats):
+            for s, step in cfgs.items():    # alternate inside a repeat
+                times[s].append(time_ms(step, args.iters))
+        for s in cfgs:
+            r = {"shape": f"B{B} H{H} S{s} D{D}", "causal": int(causal),
+                 "ragged": int(s % 128 != 0), "op": "public fwd+bwd",
+                 "fwd_bwd_ms": stats(times[s]),
+                 "peak_mib": round(peak[s], 1)}
+            if s != S_al:
+                r["vs_next_aligned"] = (statistics.median(times[s])
+                                        / statistics.median(times[S_al]))
+            print(json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", action="store_true",
+                    help="time the public op fwd+bwd at the ragged shapes "
+                         "(ViT-L S = 197 full, S = 1000 causal) and at the "
+                         "next aligned S; --shapes then indexes that list")
     ap.add_argument("--causal", choices=["0", "1", "both"], default="1")
     ap.add_argument("--map", choices=["0", "1", "both", "env"], default="env",
                     help="workgroup map: 0 legacy, 1 balanced, both = "
@@ -97,6 +157,8 @@ def main():
 
     ext = ops.load_extension()
     assert ext is not None
+    if args.ragged:
+        return run_ragged(args)
     causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
     pick = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}
     # a configuration is a (map, tr) pair

@@ -2,7 +2,8 @@
 
 BASELINE.json: "ViT-Large 4k-batch auto-SPMD (mixed DP+TP,
 reduce-scatter reshard) on 8x MI355X". Attention reuses the gfx950 flash
-kernel (non-causal); no torchvision dependency (not in the image).
+kernel (non-causal; S = 197 runs its ragged-tail instantiation); no
+torchvision dependency (not in the image).
 """
 from __future__ import annotations
 

@@ -1,12 +1,14 @@
-"""Flash attention as a custom op: HIP kernel forward on gfx950.
+"""Flash attention as a custom op: HIP kernels forward and backward on gfx950.
 
-Forward: hand-written CDNA4 flash kernel (csrc/attn_fwd.hip) — online
-softmax, MFMA 16x16x32 bf16 tiles, K/V staged through LDS with XOR swizzle.
-Backward: recompute-based composite (P from saved LSE + batched GEMMs on
-hipBLASLt) — the classic flash backward; the fused HIP backward is a later
-optimization.
+Forward: hand-written CDNA4 flash kernel (csrc/attn_kernels.hip) — online
+softmax, MFMA 16x16x32 bf16 tiles, K/V staged through swizzled LDS images.
+Backward: two hand-written kernels from the same file (dq, and dk+dv), which
+recompute P from the saved LSE; `flash_attention_bwd_pack` writes the three
+gradients straight into one [B, S, 3*H*D] buffer.
 
-CPU fallback implements the same math in aten for tests.
+The kernels take bf16 q/k/v of one shape [B, H, S, D] with D in {64, 128},
+any S >= 1 and any last-dim-contiguous strides.  Everything else (Sq != Sk,
+other head dims or dtypes) and the CPU run the same math in aten.
 """
 from __future__ import annotations
 
@@ -67,10 +69,11 @@ def _fwd_cpu(q, k, v, causal):
 
 def _kernel_ok(q, k, v):
     """The HIP kernel's supported envelope. Discovery probes this op with
-    arbitrarily sharded shapes — anything outside goes to the math path."""
+    arbitrarily sharded shapes — anything outside goes to the math path.
+    Any sequence length is inside (S % 128 != 0 runs the ragged kernels)."""
     return (q.dtype == torch.bfloat16 and q.dim() == 4
             and q.shape == k.shape and q.shape == v.shape
-            and q.shape[-1] in (64, 128) and q.shape[2] % 128 == 0)
+            and q.shape[-1] in (64, 128) and q.numel() > 0)
 
 
 def _fwd_cuda(q, k, v, causal):

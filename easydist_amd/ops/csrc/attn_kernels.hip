@@ -1,5 +1,5 @@
 // Flash attention forward and backward for gfx950 (bf16, causal or full,
-// D in {64, 128}).
+// D in {64, 128}, any S >= 1; S % 128 == 0 keeps its own instantiation).
 //
 // All four kernels share one structure: one workgroup = 8 waves = one
 // 128-row block (q rows in fwd/dq, keys in dkv) of one (batch, head),
@@ -117,6 +117,33 @@ template <int D, bool TR> constexpr int dkv_lds_elems() {
 }
 
 
+// ---- RAGGED: any S >= 1 ----------------------------------------------------
+// RAGGED = false is the S % 128 == 0 code, exactly as it was measured:
+// rag_row is the identity there and nblk keeps its spelling, so the
+// compiler emits the same instructions as before the parameter existed.
+// RAGGED = true is picked by the launch code for every other S and differs
+// in the ROW INDEX of its global loads only: rag_row clamps it to S - 1,
+// so no lane forms an address past the last row, the loads stay branch-free
+// (one v_min each; no tile-uniform test is needed, and the schedule stays
+// that of the aligned kernels), and a row >= S arrives as a copy of row
+// S - 1: finite, never uninitialised.  The forward's own q rows >= S are
+// zeros, as they always were.  Tile order and per-element arithmetic are
+// those of RAGGED = false on the same tensors padded to a multiple of 128.
+// A key or q column >= S is masked wherever it could contribute, masked
+// probabilities are exact zeros and 0 * (a copied row) is 0; a q or key
+// row >= S that a wave owns computes what row S - 1 computes, an MFMA
+// keeps rows apart, and such accumulator rows are never stored.  No q row
+// < S can be fully masked (under the causal mask row i always sees key
+// i), so the -1e30 sentinel and 1 / l_run need no special case here
+// either: do not add one.  Every wave, including one whose 16 rows are all
+// >= S, walks the same block-uniform tile loop and so reaches every
+// __syncthreads(), with EXEC all ones at every transposed read.
+template <bool RAGGED>
+DEVINL int rag_row(int row, int S) {
+  if constexpr (RAGGED) return min(row, S - 1);
+  else return row;
+}
+
 // ---- shared pieces of the swapped-operand (S^T) form ----------------------
 // pack a C-layout f32 fragment row-pair into bf16x2 words
 DEVINL void swp_pack(const f32x4* sacc, int nj, unsigned pk[][2]) {
@@ -164,9 +191,12 @@ DEVINL bf16x8v swp_butterfly(const unsigned pk[][2], int ks, int fg) {
 // butterfly above instead of an LDS strip round-trip.  The un-swapped
 // strip form, a 256-row (two fragments per wave) block and direct-from-L2
 // K reads were all A/B'd on hardware and lost (profiles/README.md).
-template <int D, bool TR>
+template <int D, bool TR, bool RAGGED = false>
 __global__ void
-__launch_bounds__(512, (D == 64 ? 4 : 1))  // waves/SIMD floor
+// waves/SIMD floor.  The aligned D = 64 kernel fits 5 (96 VGPRs); the
+// clamped row index costs the ragged one 4 more, so it runs at 4: a floor
+// of 5 there made the allocator spill 3 VGPRs to scratch.
+__launch_bounds__(512, (D == 64 ? 4 : 1))
 flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                  const bf16* __restrict__ V, bf16* __restrict__ O,
                  float* __restrict__ LSE, int B, int H, int S, bool causal,
@@ -246,7 +276,7 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
     #pragma unroll
     for (int pi = 0; pi < PF; ++pi) {
       const int e = threadIdx.x * 8 + pi * (NTHR * 8);
-      const int row = t * KB + e / D, col = e % D;
+      const int row = rag_row<RAGGED>(t * KB + e / D, S), col = e % D;
       kreg[pi] = *reinterpret_cast<const stage_t<TR>*>(
           &k[(long)row * kss + col]);
       vreg[pi] = *reinterpret_cast<const stage_t<TR>*>(
@@ -414,6 +444,10 @@ static inline int ed_attn_map_mode() {
 // dkv kernel, which stays VGPR-bound at one workgroup per CU under either
 // form and ran 0.3% (causal) to 6.8% (full) slower with the transposed
 // reads.  Read at every launch like the map.
+// This knob and EASYDIST_DKV_SWAP are A/B timing knobs for the measured
+// S % 128 == 0 shapes.  Any other S ignores both: the ragged kernels exist
+// in the default form only (fwd and dq TR = 1, dkv TR = ATTN_TR_DKV(D) and
+// SW = 0).  EASYDIST_ATTN_MAP is a kernel argument and holds for every S.
 #define ATTN_TR_FWD 1
 #define ATTN_TR_DQ 1
 #define ATTN_TR_DKV(D) ((D) == 128)
@@ -439,7 +473,8 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
               "flash_attn_fwd: q/k/v shapes must match");
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "flash_attn_fwd: D in {64,128}");
-  TORCH_CHECK(S % QB == 0, "flash_attn_fwd: S multiple of 64");
+  TORCH_CHECK(S >= 1, "flash_attn_fwd: S >= 1");
+  const bool ragged = S % (2 * QB) != 0;
   auto out = at::empty({B, H, S, D}, q.options());
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -448,7 +483,9 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
   const int map_mode = ed_attn_map_mode();
   // LDS bytes -> workgroups per 160-KiB CU, D = 64 / 128:
   //   TR = 0: 48 / 80 KiB -> 3 / 2;  TR = 1: 32 / 64 KiB -> 5 / 2
-  const bool tr = ed_attn_tr(ATTN_TR_FWD);
+  const bool tr = ragged ? ATTN_TR_FWD : ed_attn_tr(ATTN_TR_FWD);
+  static_assert(ATTN_TR_FWD == 1 && ATTN_TR_DQ == 1,
+                "the ragged fwd and dq kernels are instantiated for TR = 1");
   size_t lds = sizeof(bf16) *
       (D == 64 ? (tr ? fwd_lds_elems<64, true>() : fwd_lds_elems<64, false>())
                : (tr ? fwd_lds_elems<128, true>()
@@ -457,6 +494,9 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
   auto kern = (D == 64)
       ? (tr ? flash_fwd_kernel<64, true> : flash_fwd_kernel<64, false>)
       : (tr ? flash_fwd_kernel<128, true> : flash_fwd_kernel<128, false>);
+  if (ragged)
+    kern = (D == 64) ? flash_fwd_kernel<64, true, true>
+                     : flash_fwd_kernel<128, true, true>;
   hipLaunchKernelGGL(kern, grid, block, lds, stream,
       (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
       (const bf16*)v.data_ptr(), (bf16*)out.data_ptr(),
@@ -480,7 +520,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
 // hold row fr, k-slice fg; C/D lanes hold row 4*fg+r, col fr.
 // ---------------------------------------------------------------------------
 
-template <int D, bool TR>
+template <int D, bool TR, bool RAGGED = false>
 __global__ void __launch_bounds__(512)
 flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -493,8 +533,10 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     int map_mode) {
   // 8 waves x 16 q rows: two 64-row halves share each staged K/V tile
   // (2x arithmetic intensity vs the 4-wave form) at 6+ waves/SIMD.
-  // grid: 1-D, S/128 * B*H workgroups placed by attn_block_map
-  const AttnBlock wgm = attn_block_map(blockIdx.x, S / (2 * QB), B * H,
+  // grid: 1-D, ceil(S/128) * B*H workgroups placed by attn_block_map
+  // (S / 128 spelled as before where it is exact: same code as measured)
+  const int nblk = RAGGED ? (S + 2 * QB - 1) / (2 * QB) : S / (2 * QB);
+  const AttnBlock wgm = attn_block_map(blockIdx.x, nblk, B * H,
                                        causal, map_mode);
   const int qb0 = wgm.blk * (2 * QB);
   const int bh = wgm.bh;
@@ -533,14 +575,15 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   #pragma unroll
   for (int ks = 0; ks < D / 32; ++ks) {
     qf[ks] = *reinterpret_cast<const bf16x8v*>(
-        &q[(long)(qr0 + fr) * qss + ks * 32 + fg * 8]);
+        &q[(long)rag_row<RAGGED>(qr0 + fr, S) * qss + ks * 32 + fg * 8]);
     dof[ks] = *reinterpret_cast<const bf16x8v*>(
-        &dO_[(long)(qr0 + fr) * dss + ks * 32 + fg * 8]);
+        &dO_[(long)rag_row<RAGGED>(qr0 + fr, S) * dss + ks * 32 + fg * 8]);
   }
   // swapped operands below: one q row per lane, so one lse/delta each
+  // (scalar loads: the [B,H,S] slabs start at bh * S floats, any alignment)
   const int qrow = qr0 + fr;
-  const float lse_r = lse[qrow];
-  const float dlt_r = delta[qrow];
+  const float lse_r = lse[rag_row<RAGGED>(qrow, S)];
+  const float dlt_r = delta[rag_row<RAGGED>(qrow, S)];
 
   f32x4 dq_acc[D / 16];
   #pragma unroll
@@ -557,7 +600,7 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     for (int pi = 0; pi < NV; ++pi) {
       const int e = threadIdx.x * 8 + pi * 4096;
       // row strides: the inputs may be [B,S,H,D]-layout views
-      const long row = t0 + e / D;
+      const long row = rag_row<RAGGED>(t0 + e / D, S);
       const int col = e % D;
       kreg[pi] = *reinterpret_cast<const stage_t<TR>*>(&k[row * kss + col]);
       vreg[pi] = *reinterpret_cast<const stage_t<TR>*>(&v[row * vss + col]);
@@ -662,7 +705,7 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   }
 }
 
-template <int D, int SW, bool TR>
+template <int D, int SW, bool TR, bool RAGGED = false>
 __global__ void __launch_bounds__(512)
 flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -677,7 +720,10 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   // 8 waves x 16 key rows share each staged Q/dO tile (see dq note)
   // grid: 1-D as in dq; kv block 0 is the causal-heavy one here, so the
   // map keeps the index order (heavy_last_index = false)
-  const AttnBlock wgm = attn_block_map(blockIdx.x, S / (2 * KB), B * H,
+  static_assert(!(RAGGED && SW), "ragged S runs the strip form only");
+  // ceil(S/128) key blocks (S / 128 spelled as before where it is exact)
+  const int nblk = RAGGED ? (S + 2 * KB - 1) / (2 * KB) : S / (2 * KB);
+  const AttnBlock wgm = attn_block_map(blockIdx.x, nblk, B * H,
                                        false, map_mode);
   const int kb0 = wgm.blk * (2 * KB);
   const int bh = wgm.bh;
@@ -713,9 +759,9 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   #pragma unroll
   for (int ks = 0; ks < D / 32; ++ks) {
     kf[ks] = *reinterpret_cast<const bf16x8v*>(
-        &k[(long)(kr0 + fr) * kss + ks * 32 + fg * 8]);
+        &k[(long)rag_row<RAGGED>(kr0 + fr, S) * kss + ks * 32 + fg * 8]);
     vf[ks] = *reinterpret_cast<const bf16x8v*>(
-        &v[(long)(kr0 + fr) * vss + ks * 32 + fg * 8]);
+        &v[(long)rag_row<RAGGED>(kr0 + fr, S) * vss + ks * 32 + fg * 8]);
   }
 
   f32x4 dk_acc[D / 16], dv_acc[D / 16];
@@ -734,7 +780,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     for (int pi = 0; pi < NV; ++pi) {
       const int e = threadIdx.x * 8 + pi * 4096;
       // row strides: the inputs may be [B,S,H,D]-layout views
-      const long row = t0 + e / D;
+      const long row = rag_row<RAGGED>(t0 + e / D, S);
       const int col = e % D;
       qreg[pi] = *reinterpret_cast<const stage_t<TR>*>(&q[row * qss + col]);
       dreg[pi] = *reinterpret_cast<const stage_t<TR>*>(
@@ -835,7 +881,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       #pragma unroll
       for (int j = 0; j < QB / 16; ++j) {
         int qcol = q0 + j * 16 + fr;
-        float l = lse[qcol];
+        float l = lse[rag_row<RAGGED>(qcol, S)];
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           int krow = kr0 + 4 * fg + r;
@@ -904,7 +950,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     #pragma unroll
     for (int j = 0; j < QB / 16; ++j) {
       int qcol = q0 + j * 16 + fr;
-      float dlt = delta[qcol];
+      float dlt = delta[rag_row<RAGGED>(qcol, S)];
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float ds = st_acc[j][r] * (dpt_acc[j][r] - dlt) * scale;
@@ -991,7 +1037,8 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   TORCH_CHECK(out.is_contiguous(), "flash_attn_bwd: out must be contiguous");
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "flash_attn_bwd: D in {64,128}");
-  TORCH_CHECK(S % (2 * QB) == 0, "flash_attn_bwd: S multiple of 128");
+  TORCH_CHECK(S >= 1, "flash_attn_bwd: S >= 1");
+  const bool ragged = S % (2 * QB) != 0;
   // delta = rowsum(dO * O), fp32 — one fused bf16 pass
   auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   {
@@ -1006,15 +1053,16 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
         grad.stride(0), grad.stride(1), grad.stride(2));
   }
   auto stream = at::cuda::getCurrentCUDAStream();
-  dim3 grid = ed_attn_grid(S / (2 * QB), (long)B * H, "flash_attn_bwd"),
-       block(512);
+  dim3 grid = ed_attn_grid((S + 2 * QB - 1) / (2 * QB), (long)B * H,
+                           "flash_attn_bwd"), block(512);
   const int map_mode = ed_attn_map_mode();
   // LDS bytes -> workgroups per 160-KiB CU, D = 64 / 128:
   //   dq  (K+V+K^T, or K+V under TR), double-buffered:
   //     TR = 0: 64 / 112 KiB -> 2 / 1;  TR = 1: 32 / 64 KiB -> 5 / 2
   //   dkv (Q+dO+Q^T+dO^T, or Q+dO under TR), double-buffered, + strips:
   //     TR = 0: 80 / 144 KiB -> 2 / 1;  TR = 1: 48 / 80 KiB -> 3 / 2
-  const bool tr_q = ed_attn_tr(ATTN_TR_DQ), tr_kv = ed_attn_tr(ATTN_TR_DKV(D));
+  const bool tr_q = ragged ? ATTN_TR_DQ : ed_attn_tr(ATTN_TR_DQ);
+  const bool tr_kv = ragged ? ATTN_TR_DKV(D) : ed_attn_tr(ATTN_TR_DKV(D));
   size_t lds = sizeof(bf16) *
       (D == 64 ? (tr_q ? dq_lds_elems<64, true>() : dq_lds_elems<64, false>())
                : (tr_q ? dq_lds_elems<128, true>()
@@ -1042,6 +1090,13 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
                        : flash_bwd_dkv_kernel<128, 1, false>)
               : (tr_kv ? flash_bwd_dkv_kernel<128, 0, true>
                        : flash_bwd_dkv_kernel<128, 0, false>));
+  if (ragged) {   // default forms only: see the EASYDIST_ATTN_TR note
+    qkern = (D == 64) ? flash_bwd_dq_kernel<64, true, true>
+                      : flash_bwd_dq_kernel<128, true, true>;
+    kkern = (D == 64)
+        ? flash_bwd_dkv_kernel<64, 0, ATTN_TR_DKV(64), true>
+        : flash_bwd_dkv_kernel<128, 0, ATTN_TR_DKV(128), true>;
+  }
   hipLaunchKernelGGL(qkern, grid, block, lds, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
