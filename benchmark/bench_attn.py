@@ -17,7 +17,9 @@ difference can be set against the run-to-run spread.  One JSON line per
 configuration.
 
 --ragged times a shape set of its own instead (S % 128 != 0, see
-run_ragged); without it the output is what it always was.
+run_ragged); without it the output is what it always was.  --kv-heads N
+times grouped-query attention against the expand-and-reduce a build
+without the GQA kernels needs (see run_gqa).
 """
 import argparse
 import json
@@ -132,8 +134,67 @@ def run_ragged(args):
             print(json.dumps(r), flush=True)
 
 
+def run_gqa(args, ext):
+    """--kv-heads: grouped-query attention, forward + backward through the
+    extension, with K/V of --kv-heads heads.  Two steps alternated inside
+    each repeat: "gqa", the kernels on [B, Hkv, S, D] K/V, and "expand",
+    what a build without them has to do: repeat_interleave K/V to H heads,
+    the MHA kernels, and a sum of dk/dv over each group.  --per-kernel adds
+    the device time of each flash kernel of the gqa step (the dkv grid is
+    ceil(S/128) * B * Hkv workgroups: an under-filled chip shows there)."""
+    shapes = [tuple(int(x) for x in s.split(","))
+              for s in args.gqa_shapes.split(";")]
+    causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
+    Hkv = args.kv_heads
+    for (B, H, S, D) in shapes:
+        assert H % Hkv == 0, (H, Hkv)
+        G = H // Hkv
+        bf = torch.bfloat16
+        q = torch.randn(B, H, S, D, device="cuda", dtype=bf)
+        g = torch.randn_like(q)
+        k = torch.randn(B, Hkv, S, D, device="cuda", dtype=bf)
+        v = torch.randn_like(k)
+        for causal in causals:
+            def gqa():
+                o, lse = ext.flash_attn_fwd(q, k, v, causal)
+                return ext.flash_attn_bwd(g, q, k, v, o, lse, causal)
+
+            def expand():
+                ke = k.repeat_interleave(G, dim=1)
+                ve = v.repeat_interleave(G, dim=1)
+                o, lse = ext.flash_attn_fwd(q, ke, ve, causal)
+                dq, dk, dv = ext.flash_attn_bwd(g, q, ke, ve, o, lse, causal)
+                return (dq, dk.view(B, Hkv, G, S, D).sum(2),
+                        dv.view(B, Hkv, G, S, D).sum(2))
+
+            steps = {"gqa": gqa, "expand": expand}
+            times = {n: [] for n in steps}
+            for fn in steps.values():
+                time_ms(fn, args.warm_iters, 0)
+            for _ in range(args.repeats):
+                for n, fn in steps.items():   # alternate inside a repeat
+                    times[n].append(time_ms(fn, args.iters))
+            r = {"shape": f"B{B} H{H} Hkv{Hkv} S{S} D{D}",
+                 "causal": int(causal),
+                 "dkv_workgroups": (S + 127) // 128 * B * Hkv,
+                 "fwd_bwd_ms": {n: stats(xs) for n, xs in times.items()}}
+            r["gqa_vs_expand"] = (statistics.median(times["gqa"])
+                                  / statistics.median(times["expand"]))
+            if args.per_kernel:
+                km = kernel_ms(gqa, args.iters)
+                r["kernel_ms"] = {n: round(km[tag], 4)
+                                  for n, tag in KERNELS.items() if tag in km}
+            print(json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kv-heads", type=int, default=0,
+                    help="time grouped-query attention with this many K/V "
+                         "heads against repeat_interleave + the MHA kernels "
+                         "(see run_gqa); shapes from --gqa-shapes")
+    ap.add_argument("--gqa-shapes", default="4,32,2048,128;4,32,2048,64",
+                    help="--kv-heads only: B,H,S,D;B,H,S,D;...")
     ap.add_argument("--ragged", action="store_true",
                     help="time the public op fwd+bwd at the ragged shapes "
                          "(ViT-L S = 197 full, S = 1000 causal) and at the "
@@ -159,6 +220,8 @@ def main():
     assert ext is not None
     if args.ragged:
         return run_ragged(args)
+    if args.kv_heads:
+        return run_gqa(args, ext)
     causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
     pick = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}
     # a configuration is a (map, tr) pair

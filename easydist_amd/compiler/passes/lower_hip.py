@@ -803,7 +803,10 @@ def lower_attn_pack(gm: fx.GraphModule) -> int:
     equivalent aten chain: easydist/torch/experimental/pp/split_utils.py
     has no such fusion). flash_attention_bwd_pack writes dq/dk/dv through
     output strides straight into one [B, S, 3*H*D] buffer, so the whole
-    chain becomes one node. Run AFTER lower_sdpa.
+    chain becomes one node. Run AFTER lower_sdpa. With grouped-query
+    attention dk and dv are [B,Hkv,S,D], the cat is [B, S, (H+2*Hkv)*D]
+    and the packed op lays its buffer out the same way: the match needs
+    no head counts.
     """
     flash_bwd = torch.ops.easydist_amd.flash_attention_bwd.default
     flash_pack = torch.ops.easydist_amd.flash_attention_bwd_pack.default

@@ -227,7 +227,11 @@ def _sdpa_shardable_dims(shapes, n_qkv, mask_idx):
     q = shapes[0]   # bwd's grad_out has q's [B,H,S,D] layout too
     for dim in (0, 1):
         size = q[dim]
-        if size <= 1:
+        # grouped-query attention: k/v carry Hkv <= H heads; contiguous
+        # head chunks of q and k/v line up iff the mesh divides Hkv (the
+        # strategy pool rejects a mesh that does not), and Hkv == 1 has
+        # no head shard at all
+        if any(shapes[i][dim] <= 1 for i in range(n_qkv)):
             continue
         idxs = list(range(n_qkv))
         if mask_idx is not None:
@@ -688,14 +692,18 @@ def _register_custom_ops():
 
     @register_preset(ed.flash_attention.default)
     def _fa_rule(input_shapes, args, kwargs):
-        # (q,k,v [B,H,S,D]) -> (out [B,H,S,D], lse [B,H,S])
+        # (q [B,H,S,D], k,v [B,Hkv,S,D]) -> (out [B,H,S,D], lse [B,H,S])
         if len(input_shapes[0]) != 4:
             return None, {}
         ann = ShardAnnotation.init_from_input_shapes(input_shapes)
         combs = {}
         sid = 1
         for d in (0, 1):
-            if input_shapes[0][d] <= 1:
+            # head dim: query head h reads K/V head h // G, so contiguous
+            # head chunks of q and of k/v line up iff the mesh divides Hkv
+            # (build_strategy_pool rejects a mesh that does not divide an
+            # annotated dim); Hkv == 1 has nothing to shard
+            if input_shapes[0][d] <= 1 or input_shapes[1][d] <= 1:
                 continue
             for i in range(3):
                 ann[i][d] = ShardDim.get_shard_dim(sid)
@@ -713,14 +721,15 @@ def _register_custom_ops():
 
     @register_preset(ed.flash_attention_bwd.default)
     def _fa_bwd_rule(input_shapes, args, kwargs):
-        # (grad,q,k,v,out [B,H,S,D], lse [B,H,S]) -> (dq,dk,dv)
+        # (grad,q,out [B,H,S,D], k,v [B,Hkv,S,D], lse [B,H,S]) -> (dq,dk,dv)
         if len(input_shapes) < 6 or len(input_shapes[1]) != 4:
             return None, {}
         ann = ShardAnnotation.init_from_input_shapes(input_shapes)
         combs = {}
         sid = 1
         for d in (0, 1):
-            if input_shapes[1][d] <= 1:
+            # head dim only when Hkv > 1: see _fa_rule
+            if input_shapes[1][d] <= 1 or input_shapes[2][d] <= 1:
                 continue
             for i in range(6):
                 ann[i][d] = ShardDim.get_shard_dim(sid)

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -25,6 +26,8 @@ class GPTConfig:
     block_size: int = 1024
     dropout: float = 0.0             # benchmarks run dropout-free
     bias: bool = True
+    # K/V heads (grouped-query attention); None = n_head, plain MHA
+    n_kv_head: Optional[int] = None
 
 
 GPT2_SMALL = GPTConfig()
@@ -47,20 +50,32 @@ class CausalSelfAttention(nn.Module):
         super().__init__()
         assert cfg.n_embd % cfg.n_head == 0
         self.n_head = cfg.n_head
+        self.n_kv_head = cfg.n_head if cfg.n_kv_head is None \
+            else cfg.n_kv_head
+        assert self.n_kv_head >= 1 and cfg.n_head % self.n_kv_head == 0, \
+            (cfg.n_head, self.n_kv_head)
         self.n_embd = cfg.n_embd
         self.sp_group = None
-        self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd, bias=cfg.bias)
+        hd = cfg.n_embd // cfg.n_head
+        # q, k, v column blocks: [H*hd, Hkv*hd, Hkv*hd] (3 * n_embd for MHA)
+        self.c_attn = nn.Linear(cfg.n_embd,
+                                (cfg.n_head + 2 * self.n_kv_head) * hd,
+                                bias=cfg.bias)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd, bias=cfg.bias)
 
     def forward(self, x):
         from ..ops import attention, ring_attention
         B, T, C = x.shape
         qkv = self.c_attn(x)
-        q, k, v = qkv.split(self.n_embd, dim=2)
         hd = C // self.n_head
+        if self.n_kv_head == self.n_head:
+            q, k, v = qkv.split(self.n_embd, dim=2)
+        else:
+            q, k, v = qkv.split([C, self.n_kv_head * hd,
+                                 self.n_kv_head * hd], dim=2)
         q = q.view(B, T, self.n_head, hd).transpose(1, 2)
-        k = k.view(B, T, self.n_head, hd).transpose(1, 2)
-        v = v.view(B, T, self.n_head, hd).transpose(1, 2)
+        k = k.view(B, T, self.n_kv_head, hd).transpose(1, 2)
+        v = v.view(B, T, self.n_kv_head, hd).transpose(1, 2)
         if self.sp_group is not None:
             y = ring_attention.ring_attention(q, k, v, group=self.sp_group,
                                               causal=True)

@@ -88,6 +88,9 @@ class TPSelfAttention(nn.Module):
     def __init__(self, cfg: GPTConfig, tp, group):
         super().__init__()
         assert cfg.n_head % tp == 0, (cfg.n_head, tp)
+        assert cfg.n_kv_head in (None, cfg.n_head), \
+            "tensor-parallel GPT is multi-head only (no grouped-query " \
+            "attention)"
         self.n_head_local = cfg.n_head // tp
         self.n_embd = cfg.n_embd
         self.group = group

@@ -39,10 +39,14 @@ class MoEConfig:
     ffn_hidden: int = 14336
     capacity_factor: float = 1.25
     bias: bool = False
+    # K/V heads (grouped-query attention); None = n_head, plain MHA
+    n_kv_head: Optional[int] = None
 
 
 # Mixtral-8x7B shape (per-layer geometry; n_layer reduced variants below)
 MIXTRAL_8X7B = MoEConfig(n_layer=32)
+# the same with the real model's 8 K/V heads (G = 4)
+MIXTRAL_8X7B_GQA = MoEConfig(n_layer=32, n_kv_head=8)
 MIXTRAL_SMALL = MoEConfig(vocab_size=1024, n_layer=2, n_head=4, n_embd=256,
                           block_size=128, n_experts=4, top_k=2,
                           ffn_hidden=512)
@@ -142,6 +146,7 @@ class MoEBlock(nn.Module):
         self.ln_1 = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
         from .gpt import CausalSelfAttention, GPTConfig
         acfg = GPTConfig(n_embd=cfg.n_embd, n_head=cfg.n_head,
+                         n_kv_head=cfg.n_kv_head,
                          bias=cfg.bias, block_size=cfg.block_size)
         self.attn = CausalSelfAttention(acfg)
         self.ln_2 = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)

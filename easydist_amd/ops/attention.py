@@ -4,11 +4,17 @@ Forward: hand-written CDNA4 flash kernel (csrc/attn_kernels.hip) — online
 softmax, MFMA 16x16x32 bf16 tiles, K/V staged through swizzled LDS images.
 Backward: two hand-written kernels from the same file (dq, and dk+dv), which
 recompute P from the saved LSE; `flash_attention_bwd_pack` writes the three
-gradients straight into one [B, S, 3*H*D] buffer.
+gradients straight into one [B, S, (H + 2*Hkv)*D] buffer.
 
-The kernels take bf16 q/k/v of one shape [B, H, S, D] with D in {64, 128},
-any S >= 1 and any last-dim-contiguous strides.  Everything else (Sq != Sk,
-other head dims or dtypes) and the CPU run the same math in aten.
+The kernels take bf16 q [B, H, S, D] and k, v [B, Hkv, S, D] with
+H % Hkv == 0, D in {64, 128}, any S >= 1 and any last-dim-contiguous
+strides.  Hkv < H is grouped-query attention in torch's repeat_interleave
+convention: with G = H // Hkv, query head h attends K/V head h // G; dk and
+dv have K/V's shape, the sum over a group taken in fp32 inside the dkv
+kernel and rounded once.  Everything else (Sq != Sk, other head dims or
+dtypes) and the CPU run the same math in aten.  A query head count that is
+no multiple of the K/V head count is an error everywhere: nothing
+broadcasts.
 """
 from __future__ import annotations
 
@@ -24,15 +30,45 @@ lib.define("flash_attention(Tensor q, Tensor k, Tensor v, bool causal) "
            "-> (Tensor, Tensor)")
 lib.define("flash_attention_bwd(Tensor grad, Tensor q, Tensor k, Tensor v, "
            "Tensor out, Tensor lse, bool causal) -> (Tensor, Tensor, Tensor)")
-# packed variant: dq/dk/dv written straight into one [B, S, 3*H*D] buffer
+# packed variant: dq/dk/dv written straight into one [B, S, (H + 2*Hkv)*D]
+# buffer, dq at column 0, dk at H*D, dv at (H + Hkv)*D
 # (the qkv-projection-backward layout) — the lowering pass substitutes it
 # for the flash_bwd -> transpose -> clone -> cat chain (lower_hip.py)
 lib.define("flash_attention_bwd_pack(Tensor grad, Tensor q, Tensor k, "
            "Tensor v, Tensor out, Tensor lse, bool causal) -> Tensor")
 
 
+def _group(q, k, v):
+    """G = H // Hkv of q [B, H, S, D] and k, v [B, Hkv, T, D]."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        return 1        # no head dim to group: plain matmul semantics
+    H, Hkv = q.shape[1], k.shape[1]
+    if v.shape[1] != Hkv or Hkv < 1 or H % Hkv != 0:
+        raise ValueError(
+            f"flash_attention: {H} query heads need a K/V head count that "
+            f"divides them, the same for k and v; got k {tuple(k.shape)}, "
+            f"v {tuple(v.shape)}")
+    return H // Hkv
+
+
+def _expand_kv(t, G):
+    # [B, Hkv, T, D] -> [B, Hkv * G, T, D], head h <- head h // G
+    return t if G == 1 else t.repeat_interleave(G, dim=1)
+
+
+def _reduce_kv(d, G, dtype):
+    # fp32 [B, Hkv * G, T, D] -> [B, Hkv, T, D]: the group sum in fp32,
+    # one rounding
+    if G > 1:
+        B, H, T, D = d.shape
+        d = d.view(B, H // G, G, T, D).sum(2)
+    return d.to(dtype)
+
+
 def _math_fwd(q, k, v, causal):
-    # q,k,v: [B, H, S, D]
+    # q: [B, H, S, D]; k,v: [B, Hkv, T, D]
+    G = _group(q, k, v)
+    k, v = _expand_kv(k, G), _expand_kv(v, G)
     scale = 1.0 / math.sqrt(q.shape[-1])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
@@ -46,6 +82,9 @@ def _math_fwd(q, k, v, causal):
 
 
 def _math_bwd(grad, q, k, v, out, lse, causal):
+    G = _group(q, k, v)
+    kdt, vdt = k.dtype, v.dtype
+    k, v = _expand_kv(k, G), _expand_kv(v, G)
     scale = 1.0 / math.sqrt(q.shape[-1])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
@@ -60,7 +99,7 @@ def _math_bwd(grad, q, k, v, out, lse, causal):
     ds = p * (dp - d) * scale
     dq = torch.matmul(ds, k.float())
     dk = torch.matmul(ds.transpose(-1, -2), q.float())
-    return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
+    return dq.to(q.dtype), _reduce_kv(dk, G, kdt), _reduce_kv(dv, G, vdt)
 
 
 def _fwd_cpu(q, k, v, causal):
@@ -70,10 +109,15 @@ def _fwd_cpu(q, k, v, causal):
 def _kernel_ok(q, k, v):
     """The HIP kernel's supported envelope. Discovery probes this op with
     arbitrarily sharded shapes — anything outside goes to the math path.
-    Any sequence length is inside (S % 128 != 0 runs the ragged kernels)."""
-    return (q.dtype == torch.bfloat16 and q.dim() == 4
-            and q.shape == k.shape and q.shape == v.shape
-            and q.shape[-1] in (64, 128) and q.numel() > 0)
+    Any sequence length is inside (S % 128 != 0 runs the ragged kernels),
+    and so is any K/V head count that divides q's (the GQA kernels)."""
+    return (q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16
+            and v.dtype == torch.bfloat16
+            and q.dim() == 4 and k.dim() == 4 and k.shape == v.shape
+            and k.shape[0] == q.shape[0] and k.shape[2:] == q.shape[2:]
+            and q.numel() > 0 and k.numel() > 0
+            and q.shape[1] % k.shape[1] == 0
+            and q.shape[-1] in (64, 128))
 
 
 def _fwd_cuda(q, k, v, causal):
@@ -101,8 +145,8 @@ def _bwd_cuda(grad, q, k, v, out, lse, causal):
 
 
 def _pack3(dq, dk, dv):
-    B, H, S, D = dq.shape
-    return torch.cat([d.transpose(1, 2).reshape(B, S, H * D)
+    B, _, S, D = dq.shape
+    return torch.cat([d.transpose(1, 2).reshape(B, S, d.shape[1] * D)
                       for d in (dq, dk, dv)], dim=-1)
 
 
@@ -144,7 +188,7 @@ def _fab_fake(grad, q, k, v, out, lse, causal):
 @torch.library.register_fake("easydist_amd::flash_attention_bwd_pack")
 def _fabp_fake(grad, q, k, v, out, lse, causal):
     B, H, S, D = q.shape
-    return q.new_empty((B, S, 3 * H * D))
+    return q.new_empty((B, S, (H + 2 * k.shape[1]) * D))
 
 
 def _fa_backward(ctx, grad_out, grad_lse):

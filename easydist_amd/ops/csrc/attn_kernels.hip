@@ -1,5 +1,6 @@
 // Flash attention forward and backward for gfx950 (bf16, causal or full,
-// D in {64, 128}, any S >= 1; S % 128 == 0 keeps its own instantiation).
+// D in {64, 128}, any S >= 1; S % 128 == 0 keeps its own instantiation;
+// K/V may have fewer heads than Q, see GQA below).
 //
 // All four kernels share one structure: one workgroup = 8 waves = one
 // 128-row block (q rows in fwd/dq, keys in dkv) of one (batch, head),
@@ -144,6 +145,17 @@ DEVINL int rag_row(int row, int S) {
   else return row;
 }
 
+// ---- GQA: fewer K/V heads than query heads ----------------------------------
+// K and V are [B, Hkv, S, D] with H = G * Hkv, and query head h attends K/V
+// head h / G (torch's repeat_interleave convention).  GQA = false is the
+// Hkv == H code as it was measured: the G argument is never read there.
+// fwd and dq differ in the head of their K/V base pointer only.  dkv runs
+// one workgroup per key block of a K/V head and walks the Q/dO tiles of
+// its G query heads in one loop, summing into the same fp32 accumulators:
+// dk and dv are rounded to bf16 once, with no atomics and no second pass.
+// GQA exists in the default forms only (fwd and dq TR = 1, dkv SW = 0 and
+// TR = ATTN_TR_DKV(D)), like RAGGED.
+
 // ---- shared pieces of the swapped-operand (S^T) form ----------------------
 // pack a C-layout f32 fragment row-pair into bf16x2 words
 DEVINL void swp_pack(const f32x4* sacc, int nj, unsigned pk[][2]) {
@@ -191,7 +203,7 @@ DEVINL bf16x8v swp_butterfly(const unsigned pk[][2], int ks, int fg) {
 // butterfly above instead of an LDS strip round-trip.  The un-swapped
 // strip form, a 256-row (two fragments per wave) block and direct-from-L2
 // K reads were all A/B'd on hardware and lost (profiles/README.md).
-template <int D, bool TR, bool RAGGED = false>
+template <int D, bool TR, bool RAGGED = false, bool GQA = false>
 __global__ void
 // waves/SIMD floor.  The aligned D = 64 kernel fits 5 (96 VGPRs); the
 // clamped row index costs the ragged one 4 more, so it runs at 4: a floor
@@ -202,7 +214,7 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                  float* __restrict__ LSE, int B, int H, int S, bool causal,
                  float scale,
                  long qsb, long qsh, long qss, long ksb, long ksh, long kss,
-                 long vsb, long vsh, long vss, int map_mode) {
+                 long vsb, long vsh, long vss, int map_mode, int G) {
   // grid: 1-D, ceil(S/QBLK) * B*H workgroups placed by attn_block_map
   // (attn_block_map.h); 8 waves of one 16-row fragment each.  The round-1
   // 4-wave/256-thread form ran ONE wave per SIMD (110 KB LDS) — every
@@ -217,9 +229,10 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
   // inputs may be [B,S,H,D]-layout views (the qkv split) — per-tensor
   // batch/head/row strides avoid the activation-sized .contiguous()
   // copies the round-1 wrapper made every step
+  const int hk = GQA ? h_ / G : h_;    // this head's K/V head
   const bf16* q = Q + b_ * qsb + h_ * qsh;
-  const bf16* k = K + b_ * ksb + h_ * ksh;
-  const bf16* v = V + b_ * vsb + h_ * vsh;
+  const bf16* k = K + b_ * ksb + hk * ksh;
+  const bf16* v = V + b_ * vsb + hk * vsh;
   bf16* o = O + (long)bh * S * D;
   float* lse = LSE + (long)bh * S;
 
@@ -448,12 +461,33 @@ static inline int ed_attn_map_mode() {
 // S % 128 == 0 shapes.  Any other S ignores both: the ragged kernels exist
 // in the default form only (fwd and dq TR = 1, dkv TR = ATTN_TR_DKV(D) and
 // SW = 0).  EASYDIST_ATTN_MAP is a kernel argument and holds for every S.
+// Hkv != H ignores the two knobs in the same way: the GQA kernels exist in
+// the default form only, and EASYDIST_ATTN_MAP holds.
 #define ATTN_TR_FWD 1
 #define ATTN_TR_DQ 1
 #define ATTN_TR_DKV(D) ((D) == 128)
 static inline bool ed_attn_tr(bool dflt) {
   const char* e = getenv("EASYDIST_ATTN_TR");
   return e ? atoi(e) != 0 : dflt;
+}
+
+// Shape contract of the three host entries: bf16 q [B, H, S, D] and
+// k, v [B, Hkv, S, D] with H % Hkv == 0.  Returns G = H / Hkv.
+static inline int ed_attn_group(const at::Tensor& q, const at::Tensor& k,
+                                const at::Tensor& v, const char* who) {
+  TORCH_CHECK(q.dtype() == at::kBFloat16 && q.dim() == 4, who,
+              ": q must be a 4-D bf16 tensor");
+  TORCH_CHECK(k.dtype() == at::kBFloat16 && v.dtype() == at::kBFloat16, who,
+              ": k and v must be bf16");
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes(), who,
+              ": k and v must be 4-D and of one shape");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) &&
+              k.size(3) == q.size(3), who,
+              ": k/v must agree with q in batch, sequence and head dim");
+  TORCH_CHECK(k.size(1) >= 1 && q.size(1) % k.size(1) == 0, who, ": ",
+              q.size(1), " query heads are no multiple of ", k.size(1),
+              " K/V heads");
+  return (int)(q.size(1) / k.size(1));
 }
 
 // 1-D grid of nblk * nbh workgroups: the linear id the map consumes
@@ -468,9 +502,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
                                                   const at::Tensor& v_,
                                                   bool causal) {
   auto q = ed_attn_arg(q_), k = ed_attn_arg(k_), v = ed_attn_arg(v_);
-  TORCH_CHECK(q.dtype() == at::kBFloat16 && q.dim() == 4);
-  TORCH_CHECK(q.sizes() == k.sizes() && q.sizes() == v.sizes(),
-              "flash_attn_fwd: q/k/v shapes must match");
+  const int G = ed_attn_group(q, k, v, "flash_attn_fwd");
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "flash_attn_fwd: D in {64,128}");
   TORCH_CHECK(S >= 1, "flash_attn_fwd: S >= 1");
@@ -483,9 +515,10 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
   const int map_mode = ed_attn_map_mode();
   // LDS bytes -> workgroups per 160-KiB CU, D = 64 / 128:
   //   TR = 0: 48 / 80 KiB -> 3 / 2;  TR = 1: 32 / 64 KiB -> 5 / 2
-  const bool tr = ragged ? ATTN_TR_FWD : ed_attn_tr(ATTN_TR_FWD);
+  const bool tr = (ragged || G > 1) ? ATTN_TR_FWD : ed_attn_tr(ATTN_TR_FWD);
   static_assert(ATTN_TR_FWD == 1 && ATTN_TR_DQ == 1,
-                "the ragged fwd and dq kernels are instantiated for TR = 1");
+                "the ragged and GQA fwd and dq kernels are instantiated "
+                "for TR = 1");
   size_t lds = sizeof(bf16) *
       (D == 64 ? (tr ? fwd_lds_elems<64, true>() : fwd_lds_elems<64, false>())
                : (tr ? fwd_lds_elems<128, true>()
@@ -497,13 +530,19 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
   if (ragged)
     kern = (D == 64) ? flash_fwd_kernel<64, true, true>
                      : flash_fwd_kernel<128, true, true>;
+  if (G > 1)
+    kern = (D == 64)
+        ? (ragged ? flash_fwd_kernel<64, true, true, true>
+                  : flash_fwd_kernel<64, true, false, true>)
+        : (ragged ? flash_fwd_kernel<128, true, true, true>
+                  : flash_fwd_kernel<128, true, false, true>);
   hipLaunchKernelGGL(kern, grid, block, lds, stream,
       (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
       (const bf16*)v.data_ptr(), (bf16*)out.data_ptr(),
       lse.data_ptr<float>(), B, H, S, causal, scale,
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), map_mode);
+      v.stride(0), v.stride(1), v.stride(2), map_mode, G);
   return {out, lse};
 }
 
@@ -520,7 +559,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
 // hold row fr, k-slice fg; C/D lanes hold row 4*fg+r, col fr.
 // ---------------------------------------------------------------------------
 
-template <int D, bool TR, bool RAGGED = false>
+template <int D, bool TR, bool RAGGED = false, bool GQA = false>
 __global__ void __launch_bounds__(512)
 flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -530,7 +569,7 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     long dsb, long dsh, long dss, long qsb, long qsh,
                     long qss, long ksb, long ksh, long kss, long vsb,
                     long vsh, long vss, long osb, long osh, long oss,
-                    int map_mode) {
+                    int map_mode, int G) {
   // 8 waves x 16 q rows: two 64-row halves share each staged K/V tile
   // (2x arithmetic intensity vs the 4-wave form) at 6+ waves/SIMD.
   // grid: 1-D, ceil(S/128) * B*H workgroups placed by attn_block_map
@@ -541,10 +580,11 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   const int qb0 = wgm.blk * (2 * QB);
   const int bh = wgm.bh;
   const int b_ = bh / H, h_ = bh % H;
+  const int hk = GQA ? h_ / G : h_;    // this head's K/V head
   const bf16* dO_ = dO + b_ * dsb + h_ * dsh;
   const bf16* q = Q + b_ * qsb + h_ * qsh;
-  const bf16* k = K + b_ * ksb + h_ * ksh;
-  const bf16* v = V + b_ * vsb + h_ * vsh;
+  const bf16* k = K + b_ * ksb + hk * ksh;
+  const bf16* v = V + b_ * vsb + hk * vsh;
   // output strides (elements): the packed-dqkv variant writes straight
   // into a [B,S,3,H,D] buffer, eliminating the transpose-clone-cat chain
   bf16* dq = DQ + b_ * osb + h_ * osh;
@@ -705,7 +745,7 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   }
 }
 
-template <int D, int SW, bool TR, bool RAGGED = false>
+template <int D, int SW, bool TR, bool RAGGED = false, bool GQA = false>
 __global__ void __launch_bounds__(512)
 flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -716,26 +756,36 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      long dsb, long dsh, long dss, long qsb, long qsh,
                      long qss, long ksb, long ksh, long kss, long vsb,
                      long vsh, long vss, long osb, long osh, long oss,
-                     int map_mode) {
+                     int map_mode, int G) {
   // 8 waves x 16 key rows share each staged Q/dO tile (see dq note)
   // grid: 1-D as in dq; kv block 0 is the causal-heavy one here, so the
   // map keeps the index order (heavy_last_index = false)
   static_assert(!(RAGGED && SW), "ragged S runs the strip form only");
+  static_assert(!(GQA && SW), "GQA runs the strip form only");
   // ceil(S/128) key blocks (S / 128 spelled as before where it is exact)
   const int nblk = RAGGED ? (S + 2 * KB - 1) / (2 * KB) : S / (2 * KB);
-  const AttnBlock wgm = attn_block_map(blockIdx.x, nblk, B * H,
+  // GQA: H is the QUERY head count, the grid and the map count K/V heads,
+  // bh = b * Hkv + hkv, and osb/osh are the strides of the [.., Hkv, ..]
+  // dk/dv.  The group's first query head is hkv * G, so its lse/delta
+  // slab starts at (b * H + hkv * G) * S = bh * G * S; head g of the group
+  // lies g * qsh (dsh, S) further on.
+  const int nkh = GQA ? H / G : H;
+  const AttnBlock wgm = attn_block_map(blockIdx.x, nblk, B * nkh,
                                        false, map_mode);
   const int kb0 = wgm.blk * (2 * KB);
   const int bh = wgm.bh;
-  const int b_ = bh / H, h_ = bh % H;
-  const bf16* dO_ = dO + b_ * dsb + h_ * dsh;
-  const bf16* q = Q + b_ * qsb + h_ * qsh;
+  const int b_ = bh / nkh, h_ = bh % nkh;
+  const int hq = GQA ? h_ * G : h_;
+  // GQA moves these four on at a head switch: dO_ and q with the prefetch,
+  // lse_h and delta_h with the tile being computed
+  const bf16* dO_ = dO + b_ * dsb + hq * dsh;
+  const bf16* q = Q + b_ * qsb + hq * qsh;
   const bf16* k = K + b_ * ksb + h_ * ksh;
   const bf16* v = V + b_ * vsb + h_ * vsh;
   bf16* dk = DK + b_ * osb + h_ * osh;
   bf16* dv = DV + b_ * osb + h_ * osh;
-  const float* lse = LSE + (long)bh * S;
-  const float* delta = DELTA + (long)bh * S;
+  const float* lse_h = LSE + (long)bh * (GQA ? G : 1) * S;
+  const float* delta_h = DELTA + (long)bh * (GQA ? G : 1) * S;
 
   const int lane = threadIdx.x % WAVE;
   const int wave = threadIdx.x / WAVE;
@@ -808,11 +858,35 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   q_load(q_start);
   q_store(0);
   __syncthreads();
-  const int n_qt = (S - q_start + QB - 1) / QB;
+  // GQA: one flat loop of G * n_qh iterations, head g = tt / n_qh, tile
+  // th = tt % n_qh of that head (kept as a counter, no division).  The
+  // buffer parity is that of tt, so it runs on across a head switch, and
+  // the trip count is block-uniform: every wave reaches every barrier.
+  const int n_qh = (S - q_start + QB - 1) / QB;    // tiles per query head
+  const int n_qt = GQA ? G * n_qh : n_qh;
+  int th = 0;
   for (int tt = 0; tt < n_qt; ++tt) {
-    const int q0 = q_start + tt * QB;
+    const int q0 = q_start + (GQA ? th : tt) * QB;
     const int bofs = (tt & 1) * KVBUF;
-    if (tt + 1 < n_qt) q_load(q0 + QB);
+    // this tile's lse/delta slab; the prefetch below may belong to the
+    // next head already
+    const float* lse = lse_h;
+    const float* delta = delta_h;
+    if constexpr (GQA) {
+      if (th + 1 == n_qh) {      // last tile of head g
+        th = 0;
+        lse_h += S;
+        delta_h += S;
+        q += qsh;
+        dO_ += dsh;
+        if (tt + 1 < n_qt) q_load(q_start);
+      } else {
+        ++th;
+        q_load(q0 + QB);         // th + 1 < n_qh implies tt + 1 < n_qt
+      }
+    } else {
+      if (tt + 1 < n_qt) q_load(q0 + QB);
+    }
     if (causal && q0 + QB - 1 < kr0) {
       if (tt + 1 < n_qt) q_store((tt + 1) & 1);
       __syncthreads();
@@ -1029,13 +1103,18 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
                       const at::Tensor& k_, const at::Tensor& v_,
                       const at::Tensor& out, const at::Tensor& lse,
                       bool causal, bf16* dq_p, bf16* dk_p, bf16* dv_p,
-                      long osb, long osh, long oss) {
+                      long osb, long kosb, long osh, long oss) {
+  // osb: batch stride of dq ([.., H, ..]); kosb: that of dk and dv
+  // ([.., Hkv, ..]); head and row strides are common to the three
   auto grad = ed_attn_arg(grad_);
   auto q = ed_attn_arg(q_), k = ed_attn_arg(k_), v = ed_attn_arg(v_);
-  TORCH_CHECK(q.dtype() == at::kBFloat16 && q.dim() == 4);
-  TORCH_CHECK(q.sizes() == k.sizes() && q.sizes() == v.sizes());
+  const int G = ed_attn_group(q, k, v, "flash_attn_bwd");
+  TORCH_CHECK(grad.sizes() == q.sizes() && out.sizes() == q.sizes(),
+              "flash_attn_bwd: grad and out must have q's shape");
   TORCH_CHECK(out.is_contiguous(), "flash_attn_bwd: out must be contiguous");
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == (long)B * H * S,
+              "flash_attn_bwd: lse must be a contiguous [B, H, S]");
   TORCH_CHECK(D == 64 || D == 128, "flash_attn_bwd: D in {64,128}");
   TORCH_CHECK(S >= 1, "flash_attn_bwd: S >= 1");
   const bool ragged = S % (2 * QB) != 0;
@@ -1061,8 +1140,9 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   //     TR = 0: 64 / 112 KiB -> 2 / 1;  TR = 1: 32 / 64 KiB -> 5 / 2
   //   dkv (Q+dO+Q^T+dO^T, or Q+dO under TR), double-buffered, + strips:
   //     TR = 0: 80 / 144 KiB -> 2 / 1;  TR = 1: 48 / 80 KiB -> 3 / 2
-  const bool tr_q = ragged ? ATTN_TR_DQ : ed_attn_tr(ATTN_TR_DQ);
-  const bool tr_kv = ragged ? ATTN_TR_DKV(D) : ed_attn_tr(ATTN_TR_DKV(D));
+  const bool dflt = ragged || G > 1;   // default forms only
+  const bool tr_q = dflt ? ATTN_TR_DQ : ed_attn_tr(ATTN_TR_DQ);
+  const bool tr_kv = dflt ? ATTN_TR_DKV(D) : ed_attn_tr(ATTN_TR_DKV(D));
   size_t lds = sizeof(bf16) *
       (D == 64 ? (tr_q ? dq_lds_elems<64, true>() : dq_lds_elems<64, false>())
                : (tr_q ? dq_lds_elems<128, true>()
@@ -1097,6 +1177,24 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
         ? flash_bwd_dkv_kernel<64, 0, ATTN_TR_DKV(64), true>
         : flash_bwd_dkv_kernel<128, 0, ATTN_TR_DKV(128), true>;
   }
+  // dkv: one workgroup per key block of a K/V head (the same grid as dq
+  // when Hkv == H)
+  dim3 grid_kv = grid;
+  if (G > 1) {    // default forms only, as for ragged S
+    grid_kv = ed_attn_grid((S + 2 * KB - 1) / (2 * KB), (long)B * (H / G),
+                           "flash_attn_bwd");
+    qkern = (D == 64)
+        ? (ragged ? flash_bwd_dq_kernel<64, true, true, true>
+                  : flash_bwd_dq_kernel<64, true, false, true>)
+        : (ragged ? flash_bwd_dq_kernel<128, true, true, true>
+                  : flash_bwd_dq_kernel<128, true, false, true>);
+    kkern = (D == 64)
+        ? (ragged ? flash_bwd_dkv_kernel<64, 0, ATTN_TR_DKV(64), true, true>
+                  : flash_bwd_dkv_kernel<64, 0, ATTN_TR_DKV(64), false, true>)
+        : (ragged
+               ? flash_bwd_dkv_kernel<128, 0, ATTN_TR_DKV(128), true, true>
+               : flash_bwd_dkv_kernel<128, 0, ATTN_TR_DKV(128), false, true>);
+  }
   hipLaunchKernelGGL(qkern, grid, block, lds, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
@@ -1105,8 +1203,8 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       grad.stride(0), grad.stride(1), grad.stride(2),
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode);
-  hipLaunchKernelGGL(kkern, grid, block, lds_kv, stream,
+      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode, G);
+  hipLaunchKernelGGL(kkern, grid_kv, block, lds_kv, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
       lse.data_ptr<float>(), delta.data_ptr<float>(),
@@ -1114,7 +1212,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       grad.stride(0), grad.stride(1), grad.stride(2),
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode);
+      v.stride(0), v.stride(1), v.stride(2), kosb, osh, oss, map_mode, G);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor>
@@ -1124,17 +1222,20 @@ flash_attn_bwd(const at::Tensor& grad_, const at::Tensor& q_,
   const int B = q_.size(0), H = q_.size(1), S = q_.size(2), D = q_.size(3);
   auto opts = q_.options();
   auto dq = at::empty({B, H, S, D}, opts);
-  auto dk = at::empty({B, H, S, D}, opts);
-  auto dv = at::empty({B, H, S, D}, opts);
+  TORCH_CHECK(k_.dim() == 4, "flash_attn_bwd: k must be 4-D");
+  const int Hkv = k_.size(1);          // validated by the launch code
+  auto dk = at::empty({B, Hkv, S, D}, opts);
+  auto dv = at::empty({B, Hkv, S, D}, opts);
   flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal,
                         (bf16*)dq.data_ptr(), (bf16*)dk.data_ptr(),
                         (bf16*)dv.data_ptr(),
-                        (long)H * S * D, (long)S * D, D);
+                        (long)H * S * D, (long)Hkv * S * D, (long)S * D, D);
   return {dq, dk, dv};
 }
 
-// dq/dk/dv written straight into one [B, S, 3*H*D] buffer (the layout the
-// qkv-projection backward consumes) — replaces the reference-model
+// dq/dk/dv written straight into one [B, S, (H + 2*Hkv)*D] buffer (the
+// layout the qkv-projection backward consumes; 3*H*D when Hkv == H) —
+// replaces the reference-model
 // transpose+clone+cat chain (three strided gathers plus a cat copy,
 // ~1.2 GB of pure layout traffic per GPT layer at batch 64).
 at::Tensor
@@ -1143,12 +1244,16 @@ flash_attn_bwd_pack(const at::Tensor& grad_, const at::Tensor& q_,
                     const at::Tensor& out, const at::Tensor& lse,
                     bool causal) {
   const long B = q_.size(0), H = q_.size(1), S = q_.size(2), D = q_.size(3);
-  auto dqkv = at::empty({B, S, 3 * H * D}, q_.options());
+  TORCH_CHECK(k_.dim() == 4 && k_.size(1) >= 1,
+              "flash_attn_bwd_pack: k must be 4-D");
+  const long Hkv = k_.size(1);         // validated by the launch code
+  const long W = (H + 2 * Hkv) * D;    // packed row width
+  auto dqkv = at::empty({B, S, W}, q_.options());
   bf16* base = (bf16*)dqkv.data_ptr();
-  // dq/dk/dv sections at column offsets 0, H*D, 2*H*D of the packed rows;
-  // per-(b,h,s,d) element strides: osb=S*3HD, osh=D, oss=3HD
+  // dq/dk/dv sections at column offsets 0, H*D, (H+Hkv)*D of the packed
+  // rows; per-(b,h,s,d) element strides: osb=S*W, osh=D, oss=W
   flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal,
-                        base, base + H * D, base + 2 * H * D,
-                        S * 3 * H * D, D, 3 * H * D);
+                        base, base + H * D, base + (H + Hkv) * D,
+                        S * W, S * W, D, W);
   return dqkv;
 }
