@@ -743,6 +743,30 @@ def _register_custom_ops():
             combs[sid] = [_gather(2)] * 3
         return ann, combs
 
+    @register_preset(ed.rope_qkv.default)
+    def _rope_rule(input_shapes, args, kwargs):
+        # (qkv [B,S,W], cos [S,D/2], sin [S,D/2]) -> out [B,S,W]: every row
+        # is rotated on its own with its own table row, so the batch shards
+        # alone and the sequence shards together with the tables' rows (a
+        # sequence shard carries its positions). The column dim never
+        # shards: a contiguous chunk of [q | k | v] columns is not a set of
+        # whole heads of each, so a shard would rotate the wrong columns.
+        if len(input_shapes) < 3 or len(input_shapes[0]) != 3:
+            return None, {}
+        ann = ShardAnnotation.init_from_input_shapes(input_shapes)
+        combs = {}
+        sid = 1
+        if input_shapes[0][0] > 1:
+            ann[0][0] = ShardDim.get_shard_dim(sid)
+            combs[sid] = _gather(0)
+            sid += 1
+        if input_shapes[0][1] > 1:
+            ann[0][1] = ShardDim.get_shard_dim(sid)
+            ann[1][0] = ShardDim.get_shard_dim(sid)
+            ann[2][0] = ShardDim.get_shard_dim(sid)
+            combs[sid] = _gather(1)
+        return ann, combs
+
     @register_preset(ed.ce_fwd.default)
     def _ce_rule(input_shapes, args, kwargs):
         # (logits [N,C], targets [N]) -> (nll SUM scalar, lse [N]):

@@ -28,6 +28,10 @@ class GPTConfig:
     bias: bool = True
     # K/V heads (grouped-query attention); None = n_head, plain MHA
     n_kv_head: Optional[int] = None
+    # rotary position embeddings on q and k (ops/rope.py) instead of the
+    # learned wpe table; rope_base is the angle base (1e6 in Mixtral)
+    rope: bool = False
+    rope_base: float = 10000.0
 
 
 GPT2_SMALL = GPTConfig()
@@ -63,11 +67,19 @@ class CausalSelfAttention(nn.Module):
                                 bias=cfg.bias)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd, bias=cfg.bias)
 
-    def forward(self, x):
+    def forward(self, x, rope=None):
+        """rope: the (cos, sin) tables [T, hd/2] of this rank's positions,
+        or None for no rotation."""
         from ..ops import attention, ring_attention
         B, T, C = x.shape
         qkv = self.c_attn(x)
         hd = C // self.n_head
+        if rope is not None:
+            # on the packed projection output, before the split: everything
+            # below, ring attention included, sees rotated q and k
+            from ..ops.rope import apply_rope
+            qkv = apply_rope(qkv, rope[0], rope[1], self.n_head,
+                             self.n_kv_head)
         if self.n_kv_head == self.n_head:
             q, k, v = qkv.split(self.n_embd, dim=2)
         else:
@@ -103,10 +115,18 @@ class Block(nn.Module):
         self.ln_2 = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
         self.mlp = MLPBlock(cfg)
 
-    def forward(self, x):
-        x = x + self.attn(self.ln_1(x))
+    def forward(self, x, rope=None):
+        x = x + self.attn(self.ln_1(x), rope)
         x = x + self.mlp(self.ln_2(x))
         return x
+
+
+def register_rope_tables(module, block_size, head_dim, base):
+    """Non-persistent fp32 buffers rope_cos, rope_sin [block_size, hd/2]."""
+    from ..ops.rope import rope_tables
+    cos, sin = rope_tables(block_size, head_dim, base)
+    module.register_buffer("rope_cos", cos, persistent=False)
+    module.register_buffer("rope_sin", sin, persistent=False)
 
 
 class GPT(nn.Module):
@@ -114,12 +134,16 @@ class GPT(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.wte = nn.Embedding(cfg.vocab_size, cfg.n_embd)
-        self.wpe = nn.Embedding(cfg.block_size, cfg.n_embd)
+        if not cfg.rope:
+            self.wpe = nn.Embedding(cfg.block_size, cfg.n_embd)
         self.h = nn.ModuleList(Block(cfg) for _ in range(cfg.n_layer))
         self.ln_f = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
         self.lm_head = nn.Linear(cfg.n_embd, cfg.vocab_size, bias=False)
         self.register_buffer("pos", torch.arange(cfg.block_size),
                              persistent=False)
+        if cfg.rope:
+            register_rope_tables(self, cfg.block_size,
+                                 cfg.n_embd // cfg.n_head, cfg.rope_base)
         self.apply(self._init)
         for n, p in self.named_parameters():
             if n.endswith("c_proj.weight"):
@@ -149,14 +173,21 @@ class GPT(nn.Module):
         B, T = idx.shape
         off = getattr(self, "_sp_rank", 0) * T \
             if getattr(self, "_sp_group", None) is not None else 0
-        x = self.wte(idx) + self.wpe(self.pos[off:off + T])
+        rope = None
+        if self.cfg.rope:
+            # positions enter through q and k: a sequence shard takes its
+            # own rows of the tables
+            x = self.wte(idx)
+            rope = (self.rope_cos[off:off + T], self.rope_sin[off:off + T])
+        else:
+            x = self.wte(idx) + self.wpe(self.pos[off:off + T])
         if torch.is_autocast_enabled(x.device.type):
             # embeddings are not on autocast's cast list: without this the
             # whole residual stream runs fp32 (fp32 norms/adds + a cast
             # pair around every matmul)
             x = x.to(torch.bfloat16)
         for blk in self.h:
-            x = blk(x)
+            x = blk(x, rope)
         x = self.ln_f(x)
         return self.lm_head(x)
 

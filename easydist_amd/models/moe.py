@@ -41,12 +41,18 @@ class MoEConfig:
     bias: bool = False
     # K/V heads (grouped-query attention); None = n_head, plain MHA
     n_kv_head: Optional[int] = None
+    # rotary position embeddings on q and k instead of the learned wpe
+    rope: bool = False
+    rope_base: float = 10000.0
 
 
 # Mixtral-8x7B shape (per-layer geometry; n_layer reduced variants below)
 MIXTRAL_8X7B = MoEConfig(n_layer=32)
 # the same with the real model's 8 K/V heads (G = 4)
 MIXTRAL_8X7B_GQA = MoEConfig(n_layer=32, n_kv_head=8)
+# ... and its rotary position embeddings (base 1e6)
+MIXTRAL_8X7B_ROPE = MoEConfig(n_layer=32, n_kv_head=8, rope=True,
+                              rope_base=1e6)
 MIXTRAL_SMALL = MoEConfig(vocab_size=1024, n_layer=2, n_head=4, n_embd=256,
                           block_size=128, n_experts=4, top_k=2,
                           ffn_hidden=512)
@@ -147,13 +153,14 @@ class MoEBlock(nn.Module):
         from .gpt import CausalSelfAttention, GPTConfig
         acfg = GPTConfig(n_embd=cfg.n_embd, n_head=cfg.n_head,
                          n_kv_head=cfg.n_kv_head,
+                         rope=cfg.rope, rope_base=cfg.rope_base,
                          bias=cfg.bias, block_size=cfg.block_size)
         self.attn = CausalSelfAttention(acfg)
         self.ln_2 = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
         self.moe = MoELayer(cfg, ep_group)
 
-    def forward(self, x):
-        x = x + self.attn(self.ln_1(x))
+    def forward(self, x, rope=None):
+        x = x + self.attn(self.ln_1(x), rope)
         x = x + self.moe(self.ln_2(x))
         return x
 
@@ -165,24 +172,35 @@ class MoEGPT(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.wte = nn.Embedding(cfg.vocab_size, cfg.n_embd)
-        self.wpe = nn.Embedding(cfg.block_size, cfg.n_embd)
+        if not cfg.rope:
+            self.wpe = nn.Embedding(cfg.block_size, cfg.n_embd)
         self.h = nn.ModuleList(MoEBlock(cfg, ep_group)
                                for _ in range(cfg.n_layer))
         self.ln_f = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
         self.lm_head = nn.Linear(cfg.n_embd, cfg.vocab_size, bias=False)
         self.register_buffer("pos", torch.arange(cfg.block_size),
                              persistent=False)
+        if cfg.rope:
+            from .gpt import register_rope_tables
+            register_rope_tables(self, cfg.block_size,
+                                 cfg.n_embd // cfg.n_head, cfg.rope_base)
         nn.init.normal_(self.wte.weight, std=0.02)
-        nn.init.normal_(self.wpe.weight, std=0.02)
+        if not cfg.rope:
+            nn.init.normal_(self.wpe.weight, std=0.02)
         nn.init.normal_(self.lm_head.weight, std=0.02)
 
     def forward(self, idx):
         B, T = idx.shape
-        x = self.wte(idx) + self.wpe(self.pos[:T])
+        rope = None
+        if self.cfg.rope:
+            x = self.wte(idx)
+            rope = (self.rope_cos[:T], self.rope_sin[:T])
+        else:
+            x = self.wte(idx) + self.wpe(self.pos[:T])
         if torch.is_autocast_enabled(x.device.type):
             x = x.to(torch.bfloat16)   # keep the residual stream bf16
         for blk in self.h:
-            x = blk(x)
+            x = blk(x, rope)
         return self.lm_head(self.ln_f(x))
 
     def loss(self, idx, targets):

@@ -67,6 +67,9 @@ flash_attn_bwd_pack(const at::Tensor& grad, const at::Tensor& q,
                     const at::Tensor& k, const at::Tensor& v,
                     const at::Tensor& out, const at::Tensor& lse,
                     bool causal);
+at::Tensor rope_qkv(const at::Tensor& qkv, const at::Tensor& cos,
+                    const at::Tensor& sin, int64_t n_head, int64_t n_kv_head,
+                    bool inverse);
 
 // wrappers adapting std::vector<bool> / TensorList signatures
 static std::tuple<at::Tensor, at::Tensor, at::Tensor>
@@ -144,6 +147,8 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
         "Tensor out, Tensor lse, bool causal) -> (Tensor, Tensor, Tensor)");
   m.def("flash_attn_bwd_pack(Tensor grad, Tensor q, Tensor k, Tensor v, "
         "Tensor out, Tensor lse, bool causal) -> Tensor");
+  m.def("rope_qkv(Tensor qkv, Tensor cos, Tensor sin, int n_head, "
+        "int n_kv_head, bool inverse) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
@@ -168,6 +173,7 @@ TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
   m.impl("flash_attn_fwd", flash_attn_fwd);
   m.impl("flash_attn_bwd", flash_attn_bwd);
   m.impl("flash_attn_bwd_pack", flash_attn_bwd_pack);
+  m.impl("rope_qkv", rope_qkv);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {}

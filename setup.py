@@ -20,6 +20,7 @@ SRC = [
     "easydist_amd/ops/csrc/optim_kernels.hip",
     "easydist_amd/ops/csrc/gemm_kernels.hip",
     "easydist_amd/ops/csrc/attn_kernels.hip",
+    "easydist_amd/ops/csrc/rope_kernels.hip",
 ]
 
 setup(
