@@ -2,8 +2,10 @@
 """Flash attention kernel timing: fwd, dq and dkv, causal and not, under
 both workgroup maps (EASYDIST_ATTN_MAP) and both LDS forms
 (EASYDIST_ATTN_TR: 1 = one image per tile read transposed, 0 = the second
-transposed copy); the launch code reads both at every call, so one process
-can alternate them.
+transposed copy) and both dkv workgroup geometries (EASYDIST_DKV_GEOM: 0 =
+8 waves on 128 keys, 1 = 4 waves on 64 keys with the half-tile loop); the
+launch code reads all three at every call, so one process can alternate
+them.
 
 Event timings give fwd and total bwd (delta + dq + dkv).  Per-kernel
 figures for dq and dkv come from a kernel trace: either run this script
@@ -207,11 +209,22 @@ def main():
                     help="LDS form: 0 transposed copy, 1 transposed reads, "
                          "both = alternate them, env = leave EASYDIST_ATTN_TR "
                          "alone (unset: each kernel's shipped default)")
+    ap.add_argument("--dkv-geom", choices=["0", "1", "both", "env"],
+                    default="env",
+                    help="dkv geometry: 0 = 8 waves per 128-key block, 1 = 4 "
+                         "waves per 64-key block, both = alternate them, env "
+                         "= leave EASYDIST_DKV_GEOM alone (unset: the shipped "
+                         "default per head size)")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warm-iters", type=int, default=50)
     ap.add_argument("--shapes", default="all",
                     help="comma-separated indices into the shape list")
+    ap.add_argument("--bhsd", default=None,
+                    help="B,H,S,D[,Hkv];... : time these shapes through the "
+                         "extension instead of the --shapes list; any S, and "
+                         "K/V of Hkv heads when given (EASYDIST_ATTN_TR does "
+                         "not apply to ragged S or Hkv != H)")
     ap.add_argument("--per-kernel", action="store_true",
                     help="also report per-kernel device time (torch profiler)")
     args = ap.parse_args()
@@ -224,22 +237,29 @@ def main():
         return run_gqa(args, ext)
     causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
     pick = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}
-    # a configuration is a (map, tr) pair
-    maps = [(m, t) for m in pick[args.map] for t in pick[args.tr]]
+    # a configuration is a (map, tr, dkv geometry) triple
+    maps = [(m, t, g) for m in pick[args.map] for t in pick[args.tr]
+            for g in pick[args.dkv_geom]]
     shapes = SHAPES if args.shapes == "all" else \
         [SHAPES[int(i)] for i in args.shapes.split(",")]
+    if args.bhsd:
+        shapes = [tuple(int(x) for x in s.split(","))
+                  for s in args.bhsd.split(";")]
 
     def set_map(cfg):
-        m, t = cfg
+        m, t, g = cfg
         if m is not None:
             os.environ["EASYDIST_ATTN_MAP"] = m
         if t is not None:
             os.environ["EASYDIST_ATTN_TR"] = t
+        if g is not None:
+            os.environ["EASYDIST_DKV_GEOM"] = g
 
-    for (B, H, S, D) in shapes:
+    for (B, H, S, D, *kvh) in shapes:
+        Hkv = kvh[0] if kvh else H
         q = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16)
-        k = torch.randn_like(q)
-        v = torch.randn_like(q)
+        k = torch.randn(B, Hkv, S, D, device="cuda", dtype=torch.bfloat16)
+        v = torch.randn_like(k)
         g = torch.randn_like(q)
         for causal in causals:
             o, lse = ext.flash_attn_fwd(q, k, v, causal)
@@ -270,11 +290,15 @@ def main():
             fl_fwd = 2.0 * B * H * S * S * D * 2 * (0.5 if causal else 1.0)
             fl_bwd = fl_fwd * 2.5       # model flops of the backward
             for m in maps:
-                r = {"shape": f"B{B} H{H} S{S} D{D}", "causal": int(causal),
+                r = {"shape": f"B{B} H{H} S{S} D{D}"
+                     + (f" Hkv{Hkv}" if Hkv != H else ""),
+                     "causal": int(causal),
                      "map": m[0] if m[0] is not None
                      else os.environ.get("EASYDIST_ATTN_MAP", "1"),
                      "tr": m[1] if m[1] is not None
                      else os.environ.get("EASYDIST_ATTN_TR", "default"),
+                     "dkv_geom": m[2] if m[2] is not None
+                     else os.environ.get("EASYDIST_DKV_GEOM", "default"),
                      "fwd_ms": stats(t_fwd[m]), "bwd_ms": stats(t_bwd[m])}
                 r["fwd_tf"] = fl_fwd / r["fwd_ms"]["med"] / 1e9
                 r["bwd_tf"] = fl_bwd / r["bwd_ms"]["med"] / 1e9

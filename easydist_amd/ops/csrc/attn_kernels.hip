@@ -4,7 +4,8 @@
 //
 // All four kernels share one structure: one workgroup = 8 waves = one
 // 128-row block (q rows in fwd/dq, keys in dkv) of one (batch, head),
-// placed on the chip by attn_block_map; each wave owns 16 rows.  The
+// placed on the chip by attn_block_map; each wave owns 16 rows (dkv also
+// runs as 4 waves on a 64-key block, see flash_bwd_dkv_kernel).  The
 // 64-row tiles of the other operand pair are register-prefetched from
 // global memory and double-buffered in LDS, one swizzled row-major image
 // per tile that is read by rows (ds_read_b128) and by columns
@@ -113,8 +114,8 @@ template <int D, bool TR> constexpr int fwd_lds_elems() {
 template <int D, bool TR> constexpr int dq_lds_elems() {
   return 2 * ((TR ? 2 : 3) * KB * D) + (TR ? 0 : 8 * 16 * KB);
 }
-template <int D, bool TR> constexpr int dkv_lds_elems() {
-  return 2 * ((TR ? 2 : 4) * QB * D) + 8 * 16 * QB;   // + P^T/dS^T strips
+template <int D, bool TR, int NW = 8> constexpr int dkv_lds_elems() {
+  return 2 * ((TR ? 2 : 4) * QB * D) + NW * 16 * QB;  // + P^T/dS^T strips
 }
 
 
@@ -154,7 +155,7 @@ DEVINL int rag_row(int row, int S) {
 // its G query heads in one loop, summing into the same fp32 accumulators:
 // dk and dv are rounded to bf16 once, with no atomics and no second pass.
 // GQA exists in the default forms only (fwd and dq TR = 1, dkv SW = 0 and
-// TR = ATTN_TR_DKV(D)), like RAGGED.
+// TR = ATTN_TR_DKV(D, NW)), like RAGGED.
 
 // ---- shared pieces of the swapped-operand (S^T) form ----------------------
 // pack a C-layout f32 fragment row-pair into bf16x2 words
@@ -459,16 +460,45 @@ static inline int ed_attn_map_mode() {
 // reads.  Read at every launch like the map.
 // This knob and EASYDIST_DKV_SWAP are A/B timing knobs for the measured
 // S % 128 == 0 shapes.  Any other S ignores both: the ragged kernels exist
-// in the default form only (fwd and dq TR = 1, dkv TR = ATTN_TR_DKV(D) and
+// in the default form only (fwd and dq TR = 1, dkv TR = ATTN_TR_DKV(D, NW) and
 // SW = 0).  EASYDIST_ATTN_MAP is a kernel argument and holds for every S.
 // Hkv != H ignores the two knobs in the same way: the GQA kernels exist in
 // the default form only, and EASYDIST_ATTN_MAP holds.
 #define ATTN_TR_FWD 1
 #define ATTN_TR_DQ 1
-#define ATTN_TR_DKV(D) ((D) == 128)
+// The dkv default is per geometry (NW waves, see EASYDIST_DKV_GEOM): the
+// 4-wave form needs the 40-KiB TR = 1 request to fit its workgroups.
+#define ATTN_TR_DKV(D, NW) ((D) == 128 || (NW) == 4)
 static inline bool ed_attn_tr(bool dflt) {
   const char* e = getenv("EASYDIST_ATTN_TR");
   return e ? atoi(e) != 0 : dflt;
+}
+
+// EASYDIST_DKV_GEOM: 0 = 8 waves per dkv workgroup on a 128-key block,
+// full-tile loop (the kernel as it was); 1 = 4 waves on a 64-key block
+// with the half-tile loop, three workgroups per CU at D = 64.  Unset,
+// each head size runs what measured faster (profiles/README.md Round 10).
+// Read at every launch; it holds for every S and for GQA, each geometry
+// running its ragged and GQA kernels in that geometry's default TR form.
+// D = 128 stays on geometry 0 (two workgroups per CU at best, 5 to 34%
+// slower).  D = 64 runs geometry 1, except for a launch without the mask
+// that is only a few rounds of workgroups long: there every workgroup
+// does equal work and the time is rounds x time per workgroup.  A 64-key
+// workgroup beside two others takes 4/3 of what a 128-key workgroup takes
+// alone on its CU (64.4 against 48.9 us at B64 H12 S1024), so geometry 1
+// needs 3/4 of the rounds or fewer; 1024 workgroups on 768 slots are two
+// rounds like 512 on 256, and measured 17% slower.  Under the causal mask
+// the heavy-first order fills the tail and geometry 1 won at every size.
+#define ATTN_DKV_GEOM(D) ((D) == 64)
+static inline bool ed_dkv_geom(int D, bool causal, long S, long nbh) {
+  const char* e = getenv("EASYDIST_DKV_GEOM");
+  if (e) return atoi(e) != 0;
+  if (!ATTN_DKV_GEOM(D)) return false;
+  if (causal) return true;
+  const long cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const long r0 = ((S + 127) / 128 * nbh + cus - 1) / cus;
+  const long r1 = ((S + 63) / 64 * nbh + 3 * cus - 1) / (3 * cus);
+  return 4 * r1 <= 3 * r0;
 }
 
 // Shape contract of the three host entries: bf16 q [B, H, S, D] and
@@ -745,8 +775,24 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   }
 }
 
-template <int D, int SW, bool TR, bool RAGGED = false, bool GQA = false>
-__global__ void __launch_bounds__(512)
+// NW waves of 16 key rows each make the workgroup's key block: 8 (128 keys,
+// 512 threads, two waves per SIMD in one barrier domain) or 4 (64 keys, 256
+// threads, one wave per SIMD, so that a third and fourth workgroup fit a CU
+// where the registers allow an odd wave per SIMD).  The q tiles stay QB
+// columns wide and start at multiples of QB in both, and a 4-wave block at
+// key 128 b + 64 starts at the tile the parent's waves 4..7 start at after
+// their skipped one: every wave meets the same tiles in the same order.
+// HT walks each staged tile as two 32-column halves (S^T and dP^T, P^T and
+// the dV MFMAs, dS^T and the dK MFMAs per half) so that only half of the
+// S^T/dP^T accumulators are live at once; each dv_acc[j] and dk_acc[j]
+// still takes ks = 0 then ks = 1.  dk and dv are bit-identical across NW
+// and HT.
+template <int D, int NW> constexpr int dkv_waves_per_simd() {
+  return NW == 8 ? 2 : (D == 64 ? 3 : 2);
+}
+template <int D, int SW, bool TR, bool RAGGED = false, bool GQA = false,
+          int NW = 8, bool HT = false>
+__global__ void __launch_bounds__(NW * WAVE, (dkv_waves_per_simd<D, NW>()))
 flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      const bf16* __restrict__ K, const bf16* __restrict__ V,
                      const float* __restrict__ LSE,
@@ -757,13 +803,17 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      long qss, long ksb, long ksh, long kss, long vsb,
                      long vsh, long vss, long osb, long osh, long oss,
                      int map_mode, int G) {
-  // 8 waves x 16 key rows share each staged Q/dO tile (see dq note)
+  // NW waves x 16 key rows share each staged Q/dO tile (see dq note)
   // grid: 1-D as in dq; kv block 0 is the causal-heavy one here, so the
   // map keeps the index order (heavy_last_index = false)
   static_assert(!(RAGGED && SW), "ragged S runs the strip form only");
   static_assert(!(GQA && SW), "GQA runs the strip form only");
-  // ceil(S/128) key blocks (S / 128 spelled as before where it is exact)
-  const int nblk = RAGGED ? (S + 2 * KB - 1) / (2 * KB) : S / (2 * KB);
+  static_assert(NW == 8 || NW == 4, "8 or 4 waves per workgroup");
+  static_assert(!(HT && SW), "the half-tile loop is the strip form's");
+  constexpr int KBLK = NW * 16;          // keys per workgroup
+  constexpr int NT = NW * WAVE;          // threads per workgroup
+  // ceil(S/KBLK) key blocks (S / KBLK spelled as before where it is exact)
+  const int nblk = RAGGED ? (S + KBLK - 1) / KBLK : S / KBLK;
   // GQA: H is the QUERY head count, the grid and the map count K/V heads,
   // bh = b * Hkv + hkv, and osb/osh are the strides of the [.., Hkv, ..]
   // dk/dv.  The group's first query head is hkv * G, so its lse/delta
@@ -772,7 +822,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   const int nkh = GQA ? H / G : H;
   const AttnBlock wgm = attn_block_map(blockIdx.x, nblk, B * nkh,
                                        false, map_mode);
-  const int kb0 = wgm.blk * (2 * KB);
+  const int kb0 = wgm.blk * KBLK;
   const int bh = wgm.bh;
   const int b_ = bh / nkh, h_ = bh % nkh;
   const int hq = GQA ? h_ * G : h_;
@@ -798,7 +848,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   // only, P^T dO and dS^T Q read those images transposed
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KVBUF = (TR ? 2 : 4) * QB * D;     // elements per buffer
-  static_assert(2 * KVBUF + 8 * 16 * QB == dkv_lds_elems<D, TR>());
+  static_assert(2 * KVBUF + NW * 16 * QB == dkv_lds_elems<D, TR, NW>());
   bf16* q_lds = reinterpret_cast<bf16*>(smem);     // + buf * KVBUF
   bf16* do_lds = q_lds + QB * D;
   bf16* qt_lds = do_lds + QB * D;      // Q^T [D][QB] + lsw (TR = 0 only)
@@ -823,12 +873,12 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
 
   const int q_start = causal ? kb0 : 0;
   // register-staged Q/dO prefetch (see dq kernel note)
-  constexpr int NV = QB * D / (512 * 8);
+  constexpr int NV = QB * D / (NT * 8);
   stage_t<TR> qreg[NV], dreg[NV];
   auto q_load = [&](int t0) {
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
-      const int e = threadIdx.x * 8 + pi * 4096;
+      const int e = threadIdx.x * 8 + pi * (NT * 8);
       // row strides: the inputs may be [B,S,H,D]-layout views
       const long row = rag_row<RAGGED>(t0 + e / D, S);
       const int col = e % D;
@@ -840,7 +890,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   auto q_store = [&](int buf) {
     #pragma unroll
     for (int pi = 0; pi < NV; ++pi) {
-      const int e = threadIdx.x * 8 + pi * 4096;
+      const int e = threadIdx.x * 8 + pi * (NT * 8);
       *reinterpret_cast<stage_t<TR>*>(
           &q_lds[buf * KVBUF + isw<D, TR>(e)]) = qreg[pi];
       *reinterpret_cast<stage_t<TR>*>(
@@ -887,12 +937,103 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     } else {
       if (tt + 1 < n_qt) q_load(q0 + QB);
     }
-    if (causal && q0 + QB - 1 < kr0) {
+    // a wave whose keys all lie past the tile (waves 4..7 on a causal
+    // block's first tile; a 4-wave block has none: q0 + QB > kr0 there)
+    if (NW == 8 && causal && q0 + QB - 1 < kr0) {
       if (tt + 1 < n_qt) q_store((tt + 1) & 1);
       __syncthreads();
       continue;
     }
 
+    if constexpr (HT) {
+    // half-tile walk (strip form): per 32-column half hh the chain is
+    // 2 x D/32 x 2 MFMA, exp, strip round-trip, D/16 MFMA, strip
+    // round-trip, D/16 MFMA, with half the S^T/dP^T registers of the
+    // full-tile walk below.  The strip keeps its 16 x QB layout; half hh
+    // owns its columns 32 hh .. 32 hh + 31, so the halves never share an
+    // element and no fence separates them.
+    const bool need_mask = (causal && kr0 + 15 > q0) || (q0 + QB > S);
+    #pragma unroll
+    for (int hh = 0; hh < QB / 32; ++hh) {
+      f32x4 st_acc[2], dpt_acc[2];
+      #pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int j = 2 * hh + jj;
+        st_acc[jj] = {0.f, 0.f, 0.f, 0.f};
+        dpt_acc[jj] = {0.f, 0.f, 0.f, 0.f};
+        #pragma unroll
+        for (int ks = 0; ks < D / 32; ++ks) {
+          bf16x8v qfb = *reinterpret_cast<const bf16x8v*>(
+              &q_lds[bofs + isw<D, TR>((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+          bf16x8v dob = *reinterpret_cast<const bf16x8v*>(
+              &do_lds[bofs + isw<D, TR>((j * 16 + fr) * D + ks * 32 + fg * 8)]);
+          st_acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              kf[ks], qfb, st_acc[jj], 0, 0, 0);
+          dpt_acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              vf[ks], dob, dpt_acc[jj], 0, 0, 0);
+        }
+      }
+      // P^T into the strip for the dV mfma
+      #pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int j = 2 * hh + jj;
+        int qcol = q0 + j * 16 + fr;
+        float l = lse[rag_row<RAGGED>(qcol, S)];
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          int krow = kr0 + 4 * fg + r;
+          float p = 0.f;
+          if (!need_mask || (!(causal && krow > qcol) && qcol < S))
+            p = __expf(st_acc[jj][r] * scale - l);
+          st_acc[jj][r] = p;
+          s_lds[lsw((4 * fg + r) * QB + j * 16 + fr)] = f2bf(p);
+        }
+      }
+      lds_fence();
+      bf16x8v ptf = *reinterpret_cast<const bf16x8v*>(
+          &s_lds[lsw(fr * QB + hh * 32 + fg * 8)]);
+      #pragma unroll
+      for (int j = 0; j < D / 16; ++j) {
+        bf16x8v docol;
+        if constexpr (TR)
+          docol = tr_frag<D>(do_lds + bofs, trl, hh * 32, j * 16);
+        else
+          docol = *reinterpret_cast<const bf16x8v*>(
+              &dot_lds[bofs + lsw((j * 16 + fr) * QB + hh * 32 + fg * 8)]);
+        dv_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ptf, docol,
+                                                            dv_acc[j], 0, 0,
+                                                            0);
+      }
+      // dS^T through the same strip columns for the dK mfma
+      lds_fence();
+      #pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int j = 2 * hh + jj;
+        int qcol = q0 + j * 16 + fr;
+        float dlt = delta[rag_row<RAGGED>(qcol, S)];
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float ds = st_acc[jj][r] * (dpt_acc[jj][r] - dlt) * scale;
+          s_lds[lsw((4 * fg + r) * QB + j * 16 + fr)] = f2bf(ds);
+        }
+      }
+      lds_fence();
+      bf16x8v dstf = *reinterpret_cast<const bf16x8v*>(
+          &s_lds[lsw(fr * QB + hh * 32 + fg * 8)]);
+      #pragma unroll
+      for (int j = 0; j < D / 16; ++j) {
+        bf16x8v qcolf;
+        if constexpr (TR)
+          qcolf = tr_frag<D>(q_lds + bofs, trl, hh * 32, j * 16);
+        else
+          qcolf = *reinterpret_cast<const bf16x8v*>(
+              &qt_lds[bofs + lsw((j * 16 + fr) * QB + hh * 32 + fg * 8)]);
+        dk_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dstf, qcolf,
+                                                            dk_acc[j], 0, 0,
+                                                            0);
+      }
+    }
+    } else {
     // S^T = K Q^T and dP^T = V dO^T.  SW=1 swaps the operand order so
     // the C-layout holds the wave's 16 KEYS on the lane column and 16
     // q cols in regs — the swp_butterfly then builds the P^T/dS^T
@@ -1054,6 +1195,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                                                             0);
       }
     }
+    }   // !HT
     if (tt + 1 < n_qt) q_store((tt + 1) & 1);   // other buffer: no hazard
     __syncthreads();
   }
@@ -1067,6 +1209,34 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       dv[(long)krow * oss + j * 16 + fr] = f2bf(dv_acc[j][r]);
     }
   }
+}
+
+// The dkv instantiation and its LDS bytes for one launch.  sw and tr are
+// the A/B knobs and apply to the aligned MHA shapes only; ragged S and GQA
+// run the strip form in the geometry's default TR.  The half-tile loop is
+// the 4-wave geometry's strip form.
+using dkv_kern_t = decltype(&flash_bwd_dkv_kernel<64, 0, false>);
+struct DkvLaunch { dkv_kern_t kern; size_t lds; };
+template <int D, int NW>
+static DkvLaunch ed_dkv_pick(bool sw, bool tr, bool ragged, bool gqa) {
+  constexpr bool HT = NW == 4;
+  constexpr bool TRD = ATTN_TR_DKV(D, NW);
+  constexpr size_t L0 = sizeof(bf16) * dkv_lds_elems<D, false, NW>();
+  constexpr size_t L1 = sizeof(bf16) * dkv_lds_elems<D, true, NW>();
+  if (gqa)
+    return {ragged ? flash_bwd_dkv_kernel<D, 0, TRD, true, true, NW, HT>
+                   : flash_bwd_dkv_kernel<D, 0, TRD, false, true, NW, HT>,
+            TRD ? L1 : L0};
+  if (ragged)
+    return {flash_bwd_dkv_kernel<D, 0, TRD, true, false, NW, HT>,
+            TRD ? L1 : L0};
+  if (sw)
+    return {tr ? flash_bwd_dkv_kernel<D, 1, true, false, false, NW, false>
+               : flash_bwd_dkv_kernel<D, 1, false, false, false, NW, false>,
+            tr ? L1 : L0};
+  return {tr ? flash_bwd_dkv_kernel<D, 0, true, false, false, NW, HT>
+             : flash_bwd_dkv_kernel<D, 0, false, false, false, NW, HT>,
+          tr ? L1 : L0};
 }
 
 // delta = rowsum(dO * O) in ONE bf16 pass (the aten composite spelled
@@ -1139,62 +1309,45 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   //   dq  (K+V+K^T, or K+V under TR), double-buffered:
   //     TR = 0: 64 / 112 KiB -> 2 / 1;  TR = 1: 32 / 64 KiB -> 5 / 2
   //   dkv (Q+dO+Q^T+dO^T, or Q+dO under TR), double-buffered, + strips:
-  //     TR = 0: 80 / 144 KiB -> 2 / 1;  TR = 1: 48 / 80 KiB -> 3 / 2
+  //     8 waves: TR = 0: 80 / 144 KiB -> 2 / 1;  TR = 1: 48 / 80 KiB -> 3 / 2
+  //     4 waves: TR = 0: 72 / 136 KiB -> 2 / 1;  TR = 1: 40 / 72 KiB -> 4 / 2
   const bool dflt = ragged || G > 1;   // default forms only
   const bool tr_q = dflt ? ATTN_TR_DQ : ed_attn_tr(ATTN_TR_DQ);
-  const bool tr_kv = dflt ? ATTN_TR_DKV(D) : ed_attn_tr(ATTN_TR_DKV(D));
   size_t lds = sizeof(bf16) *
       (D == 64 ? (tr_q ? dq_lds_elems<64, true>() : dq_lds_elems<64, false>())
                : (tr_q ? dq_lds_elems<128, true>()
                        : dq_lds_elems<128, false>()));
-  size_t lds_kv = sizeof(bf16) *
-      (D == 64 ? (tr_kv ? dkv_lds_elems<64, true>()
-                        : dkv_lds_elems<64, false>())
-               : (tr_kv ? dkv_lds_elems<128, true>()
-                        : dkv_lds_elems<128, false>()));
   float scale = 1.f / sqrtf((float)D);
   auto qkern = (D == 64)
       ? (tr_q ? flash_bwd_dq_kernel<64, true> : flash_bwd_dq_kernel<64, false>)
       : (tr_q ? flash_bwd_dq_kernel<128, true>
               : flash_bwd_dq_kernel<128, false>);
-  static int swkv = []() {  // dkv butterfly measured SLOWER than the
-    const char* e = getenv("EASYDIST_DKV_SWAP");   // strip (2.11 vs 1.74
-    return e ? atoi(e) : 0;                        // ms) — default off
-  }();
-  auto kkern = (D == 64)
-      ? (swkv ? (tr_kv ? flash_bwd_dkv_kernel<64, 1, true>
-                       : flash_bwd_dkv_kernel<64, 1, false>)
-              : (tr_kv ? flash_bwd_dkv_kernel<64, 0, true>
-                       : flash_bwd_dkv_kernel<64, 0, false>))
-      : (swkv ? (tr_kv ? flash_bwd_dkv_kernel<128, 1, true>
-                       : flash_bwd_dkv_kernel<128, 1, false>)
-              : (tr_kv ? flash_bwd_dkv_kernel<128, 0, true>
-                       : flash_bwd_dkv_kernel<128, 0, false>));
-  if (ragged) {   // default forms only: see the EASYDIST_ATTN_TR note
+  if (ragged)     // default forms only: see the EASYDIST_ATTN_TR note
     qkern = (D == 64) ? flash_bwd_dq_kernel<64, true, true>
                       : flash_bwd_dq_kernel<128, true, true>;
-    kkern = (D == 64)
-        ? flash_bwd_dkv_kernel<64, 0, ATTN_TR_DKV(64), true>
-        : flash_bwd_dkv_kernel<128, 0, ATTN_TR_DKV(128), true>;
-  }
-  // dkv: one workgroup per key block of a K/V head (the same grid as dq
-  // when Hkv == H)
-  dim3 grid_kv = grid;
-  if (G > 1) {    // default forms only, as for ragged S
-    grid_kv = ed_attn_grid((S + 2 * KB - 1) / (2 * KB), (long)B * (H / G),
-                           "flash_attn_bwd");
+  if (G > 1)      // default forms only, as for ragged S
     qkern = (D == 64)
         ? (ragged ? flash_bwd_dq_kernel<64, true, true, true>
                   : flash_bwd_dq_kernel<64, true, false, true>)
         : (ragged ? flash_bwd_dq_kernel<128, true, true, true>
                   : flash_bwd_dq_kernel<128, true, false, true>);
-    kkern = (D == 64)
-        ? (ragged ? flash_bwd_dkv_kernel<64, 0, ATTN_TR_DKV(64), true, true>
-                  : flash_bwd_dkv_kernel<64, 0, ATTN_TR_DKV(64), false, true>)
-        : (ragged
-               ? flash_bwd_dkv_kernel<128, 0, ATTN_TR_DKV(128), true, true>
-               : flash_bwd_dkv_kernel<128, 0, ATTN_TR_DKV(128), false, true>);
-  }
+  // dkv: one workgroup of nw waves per block of nw * 16 keys of a K/V head
+  // (the same grid as dq when nw == 8 and Hkv == H)
+  static int swkv = []() {  // dkv butterfly measured SLOWER than the
+    const char* e = getenv("EASYDIST_DKV_SWAP");   // strip (2.11 vs 1.74
+    return e ? atoi(e) : 0;                        // ms) — default off
+  }();
+  const int nw = ed_dkv_geom(D, causal, S, (long)B * (H / G)) ? 4 : 8;
+  const bool tr_d = nw == 4 ? ATTN_TR_DKV(D, 4) : ATTN_TR_DKV(D, 8);
+  const bool tr_kv = dflt ? tr_d : ed_attn_tr(tr_d);
+  const DkvLaunch kv = (D == 64)
+      ? (nw == 4 ? ed_dkv_pick<64, 4>(swkv, tr_kv, ragged, G > 1)
+                 : ed_dkv_pick<64, 8>(swkv, tr_kv, ragged, G > 1))
+      : (nw == 4 ? ed_dkv_pick<128, 4>(swkv, tr_kv, ragged, G > 1)
+                 : ed_dkv_pick<128, 8>(swkv, tr_kv, ragged, G > 1));
+  dim3 grid_kv = ed_attn_grid((S + nw * 16 - 1) / (nw * 16),
+                              (long)B * (H / G), "flash_attn_bwd");
+  dim3 block_kv(nw * WAVE);
   hipLaunchKernelGGL(qkern, grid, block, lds, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
@@ -1204,7 +1357,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
       v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode, G);
-  hipLaunchKernelGGL(kkern, grid_kv, block, lds_kv, stream,
+  hipLaunchKernelGGL(kv.kern, grid_kv, block_kv, kv.lds, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
       lse.data_ptr<float>(), delta.data_ptr<float>(),
