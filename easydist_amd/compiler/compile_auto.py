@@ -81,12 +81,15 @@ def _compile_auto(func, tracing_mode, args, kwargs, module, opt):
                                    lower_cross_entropy, lower_gelu_bwd_fuse,
                                    lower_gelu_fwd_fuse, lower_gemm,
                                    lower_layer_norm,
-                                   lower_norm_residual_fuse, lower_sdpa)
+                                   lower_norm_residual_fuse, lower_sdpa,
+                                   lower_swiglu)
     import os as _os
     lower_layer_norm(gm)
     if _os.environ.get("EASYDIST_NORM_FUSE", "1") != "0":
         lower_norm_residual_fuse(gm)
     lower_sdpa(gm)
+    if _os.environ.get("EASYDIST_SWIGLU_FUSE", "1") != "0":
+        lower_swiglu(gm)
     if _os.environ.get("EASYDIST_ATTN_PACK", "1") != "0":
         lower_attn_pack(gm)
     lower_cross_entropy(gm)

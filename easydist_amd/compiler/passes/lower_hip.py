@@ -24,6 +24,7 @@ import torch.fx as fx
 
 from ...ops import norms as _norms  # noqa: F401  (registers the ops)
 from ...ops import gemm as _gemm    # noqa: F401
+from ...ops import swiglu as _swiglu  # noqa: F401
 
 logger = logging.getLogger(__name__)
 
@@ -960,3 +961,149 @@ def lower_gelu_fwd_fuse(gm: fx.GraphModule) -> int:
         logger.info("lower_hip: fused %d forward gelu into GEMM epilogues",
                     n_fused)
     return n_fused
+
+
+def _descendants(node: fx.Node) -> set:
+    seen, stack = set(), [node]
+    while stack:
+        for u in stack.pop().users:
+            if u not in seen:
+                seen.add(u)
+                stack.append(u)
+    return seen
+
+
+def lower_swiglu(gm: fx.GraphModule) -> int:
+    """silu(a) * b and its autograd -> easydist_amd::swiglu(+_bwd).
+
+    Forward:   mul(silu(a), b), either operand order, a and b of one shape
+               and dtype (no broadcast, no cast in between)
+            -> swiglu(a, b)
+    Backward:  dup = mul(g, silu(a)); dgate = silu_backward(mul(g, b), a),
+               the same g in both, either operand order
+            -> dgate, dup = swiglu_bwd(g, a, b)
+
+    The aten chain moves 5 activation-sized tensors forward and 9 backward
+    and keeps silu(a) alive in between; the fused kernels move 3 and 5 and
+    recompute the sigmoid from a. A forward without a matching backward
+    (an inference graph) still fuses; a backward whose pieces do not all
+    match is left alone, and so is any mul of the silu with a value derived
+    from it. In fp32 and fp64 the ops run the very aten calls they replace,
+    so the rewrite changes no bit there. Returns forward + backward fusions.
+    """
+    graph = gm.graph
+    swiglu = torch.ops.easydist_amd.swiglu.default
+    swiglu_bwd = torch.ops.easydist_amd.swiglu_bwd.default
+    n_fwd = n_bwd = 0
+
+    def same(*nodes):
+        """One shape and dtype on every node's val."""
+        vals = [_val(x) for x in nodes]
+        return all(isinstance(v, torch.Tensor) for v in vals) \
+            and all(v.shape == vals[0].shape and v.dtype == vals[0].dtype
+                    for v in vals)
+
+    def contig(*nodes):
+        """Laid out as the ops' outputs are: new contiguous tensors."""
+        return all(_val(x).is_contiguous() for x in nodes)
+
+    def is_mul(m):
+        """mul.Tensor of two different nodes."""
+        return isinstance(m, fx.Node) and m.op == "call_function" \
+            and m.target is aten.mul.Tensor and len(m.args) == 2 \
+            and not m.kwargs \
+            and all(isinstance(a, fx.Node) for a in m.args) \
+            and m.args[0] is not m.args[1]
+
+    def mul_other(m, x):
+        """The other operand of m = mul.Tensor(x, y) / (y, x), or None."""
+        if is_mul(m) and x in m.args:
+            return m.args[1] if m.args[0] is x else m.args[0]
+        return None
+
+    def fuse_fwd(n, a, b):
+        with graph.inserting_before(n):
+            fused = graph.call_function(swiglu, (a, b))
+        fused.meta = dict(n.meta)
+        order[fused] = order[n]
+        n.replace_all_uses_with(fused)
+        graph.erase_node(n)
+
+    order = {x: i for i, x in enumerate(graph.nodes)}
+    for sl in list(graph.nodes):
+        if sl.op != "call_function" or sl.target is not aten.silu.default:
+            continue
+        a = sl.args[0]
+        if not isinstance(a, fx.Node):
+            continue
+        # a product of the silu with something computed from it is never
+        # the activation: a gradient reaches back here through the loss
+        desc = _descendants(sl)
+        muls = {}         # the other operand -> mul(silu, other)
+        for n in sorted(sl.users, key=order.__getitem__):
+            other = mul_other(n, sl)
+            if other is not None and other not in muls:
+                muls[other] = n
+        taken = set()
+
+        # the triples first. silu_backward(mul(x, y), a) with mul(silu, x)
+        # and mul(silu, y) both there: one of x, y is the up operand and
+        # the other the gradient, and the activation is the product that
+        # the trace computed first.
+        for sb in list(a.users):
+            if sb.op != "call_function" or len(sb.args) != 2 \
+                    or sb.target is not aten.silu_backward.default \
+                    or sb.args[1] is not a:
+                continue
+            if not is_mul(sb.args[0]):
+                continue
+            x, y = sb.args[0].args
+            fwd, m1 = muls.get(x), muls.get(y)
+            if fwd is None or m1 is None or {fwd, m1} & taken:
+                continue
+            b, g = x, y
+            if order[m1] < order[fwd]:
+                fwd, m1, b, g = m1, fwd, y, x
+            if b in desc or not same(a, b, g, sl, fwd, m1, sb) \
+                    or not contig(fwd, m1, sb):
+                continue
+            # the fused node goes where the first of the two stood: its
+            # operands have to exist by then
+            first = m1 if order[m1] < order[sb] else sb
+            if order[g] > order[first] or order[b] > order[first]:
+                continue
+            fuse_fwd(fwd, a, b)
+            with graph.inserting_before(first):
+                bwd = graph.call_function(swiglu_bwd, (g, a, b))
+                dgate = graph.call_function(operator.getitem, (bwd, 0))
+                dup = graph.call_function(operator.getitem, (bwd, 1))
+            bwd.meta = dict(sb.meta)
+            bwd.meta["val"] = (_val(sb), _val(m1))
+            dgate.meta = dict(sb.meta)
+            dup.meta = dict(m1.meta)
+            order[bwd] = order[dgate] = order[dup] = order[first]
+            sb.replace_all_uses_with(dgate)
+            m1.replace_all_uses_with(dup)
+            graph.erase_node(sb)
+            graph.erase_node(m1)
+            taken.update((fwd, m1))
+            n_fwd += 1
+            n_bwd += 1
+
+        # a forward with no backward of this form (an inference graph)
+        for b, n in muls.items():
+            if n in taken or b in desc:
+                continue
+            if same(a, b, sl, n) and contig(n):
+                fuse_fwd(n, a, b)
+                n_fwd += 1
+
+    if n_fwd or n_bwd:
+        # the silu and the mul(g, b) that fed silu_backward die here: that
+        # is how the saved activation disappears
+        graph.eliminate_dead_code()
+        graph.lint()
+        gm.recompile()
+        logger.info("lower_hip: fused %d silu*mul into swiglu, %d backward "
+                    "triples into swiglu_bwd", n_fwd, n_bwd)
+    return n_fwd + n_bwd

@@ -767,6 +767,30 @@ def _register_custom_ops():
             combs[sid] = _gather(1)
         return ann, combs
 
+    def _swiglu_rule(n_out):
+        # elementwise on operands of one shape: every dim of size > 1
+        # shards on all operands together and every output gathers on it
+        def rule(input_shapes, args, kwargs):
+            shape = input_shapes[0]
+            if any(tuple(s) != tuple(shape) for s in input_shapes):
+                return None, {}
+            ann = ShardAnnotation.init_from_input_shapes(input_shapes)
+            combs = {}
+            sid = 1
+            for d in range(len(shape)):
+                if shape[d] <= 1:
+                    continue
+                for i in range(len(input_shapes)):
+                    ann[i][d] = ShardDim.get_shard_dim(sid)
+                combs[sid] = _gather(d) if n_out == 1 \
+                    else [_gather(d)] * n_out
+                sid += 1
+            return ann, combs
+        return rule
+
+    register_preset(ed.swiglu.default)(_swiglu_rule(1))
+    register_preset(ed.swiglu_bwd.default)(_swiglu_rule(2))
+
     @register_preset(ed.ce_fwd.default)
     def _ce_rule(input_shapes, args, kwargs):
         # (logits [N,C], targets [N]) -> (nll SUM scalar, lse [N]):

@@ -32,6 +32,12 @@ class GPTConfig:
     # learned wpe table; rope_base is the angle base (1e6 in Mixtral)
     rope: bool = False
     rope_base: float = 10000.0
+    # "gelu": c_proj(gelu(c_fc(x))), hidden width 4 * n_embd.  "swiglu": the
+    # Llama-style gated MLP c_proj(silu(c_fc(x)) * c_up(x)) through the fused
+    # op (ops/swiglu.py), hidden width ffn_hidden, by default 8/3 * n_embd
+    # rounded up to a multiple of 256
+    mlp: str = "gelu"
+    ffn_hidden: Optional[int] = None
 
 
 GPT2_SMALL = GPTConfig()
@@ -100,10 +106,26 @@ class CausalSelfAttention(nn.Module):
 class MLPBlock(nn.Module):
     def __init__(self, cfg: GPTConfig):
         super().__init__()
-        self.c_fc = nn.Linear(cfg.n_embd, 4 * cfg.n_embd, bias=cfg.bias)
-        self.c_proj = nn.Linear(4 * cfg.n_embd, cfg.n_embd, bias=cfg.bias)
+        if cfg.mlp not in ("gelu", "swiglu"):
+            raise ValueError(
+                f"GPTConfig.mlp must be 'gelu' or 'swiglu', got {cfg.mlp!r}")
+        self.gated = cfg.mlp == "swiglu"
+        if not self.gated:
+            self.c_fc = nn.Linear(cfg.n_embd, 4 * cfg.n_embd, bias=cfg.bias)
+            self.c_proj = nn.Linear(4 * cfg.n_embd, cfg.n_embd,
+                                    bias=cfg.bias)
+            return
+        hidden = cfg.ffn_hidden
+        if hidden is None:
+            hidden = -(-8 * cfg.n_embd // 3 // 256) * 256
+        self.c_fc = nn.Linear(cfg.n_embd, hidden, bias=cfg.bias)    # gate
+        self.c_up = nn.Linear(cfg.n_embd, hidden, bias=cfg.bias)
+        self.c_proj = nn.Linear(hidden, cfg.n_embd, bias=cfg.bias)
 
     def forward(self, x):
+        if self.gated:
+            from ..ops.swiglu import swiglu
+            return self.c_proj(swiglu(self.c_fc(x), self.c_up(x)))
         return self.c_proj(F.gelu(self.c_fc(x), approximate="tanh"))
 
 

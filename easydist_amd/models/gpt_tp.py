@@ -118,6 +118,9 @@ class TPSelfAttention(nn.Module):
 class TPMLP(nn.Module):
     def __init__(self, cfg: GPTConfig, tp, group):
         super().__init__()
+        if getattr(cfg, "mlp", "gelu") != "gelu":
+            raise ValueError(
+                f"GPT_TP builds the gelu MLP only; got mlp={cfg.mlp!r}")
         self.group = group
         self.c_fc = ColumnParallelLinear(cfg.n_embd, 4 * cfg.n_embd, tp,
                                          bias=cfg.bias)

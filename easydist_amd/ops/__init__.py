@@ -2,8 +2,8 @@
 
 The compute path of the framework (SURVEY.md §7 phase 5): partitioned hot
 ops in the lowered graph run as gfx950 kernels — MFMA-tiled GEMM, flash
-attention, rotary embeddings, LayerNorm fwd/bwd, fused multi-tensor Adam,
-fused cross-entropy.
+attention, rotary embeddings, fused SwiGLU, LayerNorm fwd/bwd, fused
+multi-tensor Adam, fused cross-entropy.
 Plain large GEMMs go to hipBLASLt via aten (torch.mm); everything listed
 here is a hand kernel.
 
@@ -73,6 +73,8 @@ def require_hip_ops():
 
 
 from . import attention, norms, optim, ce, gemm, moe_ops, rope  # noqa: E402
+from . import swiglu  # noqa: E402
 
 __all__ = ["attention", "norms", "optim", "ce", "gemm", "moe_ops", "rope",
-           "load_extension", "hip_ops_available", "require_hip_ops"]
+           "swiglu", "load_extension", "hip_ops_available",
+           "require_hip_ops"]

@@ -70,6 +70,10 @@ flash_attn_bwd_pack(const at::Tensor& grad, const at::Tensor& q,
 at::Tensor rope_qkv(const at::Tensor& qkv, const at::Tensor& cos,
                     const at::Tensor& sin, int64_t n_head, int64_t n_kv_head,
                     bool inverse);
+at::Tensor swiglu_fwd(const at::Tensor& gate, const at::Tensor& up);
+std::tuple<at::Tensor, at::Tensor>
+swiglu_bwd(const at::Tensor& grad, const at::Tensor& gate,
+           const at::Tensor& up);
 
 // wrappers adapting std::vector<bool> / TensorList signatures
 static std::tuple<at::Tensor, at::Tensor, at::Tensor>
@@ -149,6 +153,9 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
         "Tensor out, Tensor lse, bool causal) -> Tensor");
   m.def("rope_qkv(Tensor qkv, Tensor cos, Tensor sin, int n_head, "
         "int n_kv_head, bool inverse) -> Tensor");
+  m.def("swiglu_fwd(Tensor gate, Tensor up) -> Tensor");
+  m.def("swiglu_bwd(Tensor grad, Tensor gate, Tensor up) "
+        "-> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
@@ -174,6 +181,8 @@ TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
   m.impl("flash_attn_bwd", flash_attn_bwd);
   m.impl("flash_attn_bwd_pack", flash_attn_bwd_pack);
   m.impl("rope_qkv", rope_qkv);
+  m.impl("swiglu_fwd", swiglu_fwd);
+  m.impl("swiglu_bwd", swiglu_bwd);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {}

@@ -21,6 +21,7 @@ SRC = [
     "easydist_amd/ops/csrc/gemm_kernels.hip",
     "easydist_amd/ops/csrc/attn_kernels.hip",
     "easydist_amd/ops/csrc/rope_kernels.hip",
+    "easydist_amd/ops/csrc/swiglu_kernels.hip",
 ]
 
 setup(
