@@ -21,7 +21,9 @@ configuration.
 --ragged times a shape set of its own instead (S % 128 != 0, see
 run_ragged); without it the output is what it always was.  --kv-heads N
 times grouped-query attention against the expand-and-reduce a build
-without the GQA kernels needs (see run_gqa).
+without the GQA kernels needs (see run_gqa).  --window W times
+sliding-window causal attention against the causal kernels on the same
+tensors (see run_window).
 """
 import argparse
 import json
@@ -189,8 +191,58 @@ def run_gqa(args, ext):
             print(json.dumps(r), flush=True)
 
 
+def run_window(args, ext):
+    """--window W: sliding-window causal attention through the extension,
+    forward and backward timed apart, against the causal kernels on the
+    same tensors, the two alternated inside each repeat.  Shapes from
+    --bhsd (B,H,S,D[,Hkv]).  tile_ratio is the kv tiles a 128-row q block
+    walks under the window over those it walks under the causal mask,
+    summed over the blocks: what the time ratio should approach."""
+    W = args.window
+    for s in args.bhsd.split(";"):
+        B, H, S, D, *kvh = (int(x) for x in s.split(","))
+        Hkv = kvh[0] if kvh else H
+        bf = torch.bfloat16
+        q = torch.randn(B, H, S, D, device="cuda", dtype=bf)
+        k = torch.randn(B, Hkv, S, D, device="cuda", dtype=bf)
+        v = torch.randn_like(k)
+        g = torch.randn_like(q)
+        steps = {}
+        for name, win in (("causal", ()), ("window", (W,))):
+            o, lse = ext.flash_attn_fwd(q, k, v, True, *win)
+            steps[name] = (
+                lambda win=win: ext.flash_attn_fwd(q, k, v, True, *win),
+                lambda win=win, o=o, lse=lse: ext.flash_attn_bwd(
+                    g, q, k, v, o, lse, True, *win))
+        t = {n: ([], []) for n in steps}
+        for fwd, bwd in steps.values():
+            time_ms(fwd, args.warm_iters, 0)
+            time_ms(bwd, args.warm_iters, 0)
+        for _ in range(args.repeats):
+            for n, (fwd, bwd) in steps.items():   # alternate inside a repeat
+                t[n][0].append(time_ms(fwd, args.iters))
+                t[n][1].append(time_ms(bwd, args.iters))
+        blocks = range(0, S, 128)
+        n_c = sum((min(S, b + 128) + 63) // 64 for b in blocks)
+        n_w = sum((min(S, b + 128) + 63) // 64 - max(0, b - W + 1) // 64
+                  for b in blocks)
+        med = statistics.median
+        r = {"shape": f"B{B} H{H} S{S} D{D}"
+             + (f" Hkv{Hkv}" if Hkv != H else ""), "window": W,
+             "fwd_ms": {n: stats(t[n][0]) for n in t},
+             "bwd_ms": {n: stats(t[n][1]) for n in t},
+             "fwd_ratio": med(t["window"][0]) / med(t["causal"][0]),
+             "bwd_ratio": med(t["window"][1]) / med(t["causal"][1]),
+             "tile_ratio": n_w / n_c}
+        print(json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--window", type=int, default=0,
+                    help="time sliding-window causal attention of this "
+                         "window against the causal kernels on the same "
+                         "tensors (see run_window); shapes from --bhsd")
     ap.add_argument("--kv-heads", type=int, default=0,
                     help="time grouped-query attention with this many K/V "
                          "heads against repeat_interleave + the MHA kernels "
@@ -235,6 +287,9 @@ def main():
         return run_ragged(args)
     if args.kv_heads:
         return run_gqa(args, ext)
+    if args.window:
+        assert args.bhsd, "--window takes its shapes from --bhsd"
+        return run_window(args, ext)
     causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
     pick = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}
     # a configuration is a (map, tr, dkv geometry) triple

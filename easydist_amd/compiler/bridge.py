@@ -47,6 +47,15 @@ def _flops_of(node: fx.Node) -> float:
         if t in (ed.flash_attention_bwd.default,):
             q = shape(1)
             return 2.0 * q[0] * q[1] * q[2] * q[2] * q[3] * 5 * 0.5
+        if t in (ed.flash_attention_swa.default,
+                 ed.flash_attention_swa_bwd.default):
+            # the causal formulas with S*S/2 replaced by the band's pair
+            # count W*S - W*(W-1)/2 (W <= S; a wider window is causal)
+            fwd = t is ed.flash_attention_swa.default
+            q = shape(0 if fwd else 1)
+            w = min(int(node.args[-1]), q[2])
+            pairs = w * q[2] - w * (w - 1) / 2.0
+            return 2.0 * q[0] * q[1] * pairs * q[3] * (2 if fwd else 5)
         if t in (aten._scaled_dot_product_flash_attention.default
                  if hasattr(aten, "_scaled_dot_product_flash_attention")
                  else aten.mm.default,

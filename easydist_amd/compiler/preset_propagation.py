@@ -743,6 +743,31 @@ def _register_custom_ops():
             combs[sid] = [_gather(2)] * 3
         return ann, combs
 
+    def _swa_rule(n_in, n_out):
+        # flash_attention_swa (q, k, v) and flash_attention_swa_bwd (grad, q,
+        # k, v, out, lse): batch and head dims exactly as _fa_rule and
+        # _fa_bwd_rule.  The sequence dim does not shard and the ops have no
+        # RUNTIME_REALIZED entry: ring attention does not know windows.
+        iq = 0 if n_in == 3 else 1          # q; k follows it
+        def rule(input_shapes, args, kwargs):
+            if len(input_shapes) < n_in or len(input_shapes[iq]) != 4:
+                return None, {}
+            ann = ShardAnnotation.init_from_input_shapes(input_shapes)
+            combs = {}
+            sid = 1
+            for d in (0, 1):
+                if input_shapes[iq][d] <= 1 or input_shapes[iq + 1][d] <= 1:
+                    continue
+                for i in range(n_in):
+                    ann[i][d] = ShardDim.get_shard_dim(sid)
+                combs[sid] = [_gather(d)] * n_out
+                sid += 1
+            return ann, combs
+        return rule
+
+    register_preset(ed.flash_attention_swa.default)(_swa_rule(3, 2))
+    register_preset(ed.flash_attention_swa_bwd.default)(_swa_rule(6, 3))
+
     @register_preset(ed.rope_qkv.default)
     def _rope_rule(input_shapes, args, kwargs):
         # (qkv [B,S,W], cos [S,D/2], sin [S,D/2]) -> out [B,S,W]: every row

@@ -38,6 +38,10 @@ class GPTConfig:
     # rounded up to a multiple of 256
     mlp: str = "gelu"
     ffn_hidden: Optional[int] = None
+    # sliding-window causal attention (Mistral): token i attends tokens
+    # i - sliding_window + 1 .. i through the window flash kernels; None =
+    # plain causal attention.  Not combined with sequence parallelism.
+    sliding_window: Optional[int] = None
 
 
 GPT2_SMALL = GPTConfig()
@@ -65,6 +69,10 @@ class CausalSelfAttention(nn.Module):
         assert self.n_kv_head >= 1 and cfg.n_head % self.n_kv_head == 0, \
             (cfg.n_head, self.n_kv_head)
         self.n_embd = cfg.n_embd
+        self.sliding_window = cfg.sliding_window
+        if self.sliding_window is not None and self.sliding_window < 1:
+            raise ValueError("GPTConfig.sliding_window must be >= 1 or None, "
+                             f"got {self.sliding_window}")
         self.sp_group = None
         hd = cfg.n_embd // cfg.n_head
         # q, k, v column blocks: [H*hd, Hkv*hd, Hkv*hd] (3 * n_embd for MHA)
@@ -95,8 +103,15 @@ class CausalSelfAttention(nn.Module):
         k = k.view(B, T, self.n_kv_head, hd).transpose(1, 2)
         v = v.view(B, T, self.n_kv_head, hd).transpose(1, 2)
         if self.sp_group is not None:
+            if self.sliding_window is not None:
+                raise NotImplementedError(
+                    "sliding_window with sequence parallelism: ring "
+                    "attention does not know windows")
             y = ring_attention.ring_attention(q, k, v, group=self.sp_group,
                                               causal=True)
+        elif self.sliding_window is not None:
+            y = attention.scaled_dot_product_attention(
+                q, k, v, causal=True, window=self.sliding_window)
         else:
             y = attention.scaled_dot_product_attention(q, k, v, causal=True)
         y = y.transpose(1, 2).reshape(B, T, C)
@@ -185,6 +200,10 @@ class GPT(nn.Module):
         shard (token slice) of the batch; attention rings over the
         group; positions offset by the rank's slice start."""
         import torch.distributed as dist
+        if self.cfg.sliding_window is not None:
+            raise NotImplementedError(
+                "enable_sequence_parallel with GPTConfig.sliding_window: "
+                "ring attention does not know windows")
         self._sp_group = group
         self._sp_rank = dist.get_rank(group)
         for blk in self.h:

@@ -44,6 +44,8 @@ class MoEConfig:
     # rotary position embeddings on q and k instead of the learned wpe
     rope: bool = False
     rope_base: float = 10000.0
+    # sliding-window causal attention, as GPTConfig.sliding_window
+    sliding_window: Optional[int] = None
 
 
 # Mixtral-8x7B shape (per-layer geometry; n_layer reduced variants below)
@@ -154,6 +156,7 @@ class MoEBlock(nn.Module):
         acfg = GPTConfig(n_embd=cfg.n_embd, n_head=cfg.n_head,
                          n_kv_head=cfg.n_kv_head,
                          rope=cfg.rope, rope_base=cfg.rope_base,
+                         sliding_window=cfg.sliding_window,
                          bias=cfg.bias, block_size=cfg.block_size)
         self.attn = CausalSelfAttention(acfg)
         self.ln_2 = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)

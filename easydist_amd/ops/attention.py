@@ -15,11 +15,18 @@ kernel and rounded once.  Everything else (Sq != Sk, other head dims or
 dtypes) and the CPU run the same math in aten.  A query head count that is
 no multiple of the K/V head count is an error everywhere: nothing
 broadcasts.
+
+`flash_attention_swa` is sliding-window causal self-attention (Mistral's
+`sliding_window = W`): query row i attends keys j with i - W < j <= i, W
+keys with itself.  The window instantiations of the same three kernels walk
+only the tiles the band touches, O(S * W) with no mask tensor; W >= S is
+plain causal attention and runs the causal kernels.  The packed backward and
+the sequence-parallel (ring) rewrite do not know windows yet.
 """
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -36,6 +43,14 @@ lib.define("flash_attention_bwd(Tensor grad, Tensor q, Tensor k, Tensor v, "
 # for the flash_bwd -> transpose -> clone -> cat chain (lower_hip.py)
 lib.define("flash_attention_bwd_pack(Tensor grad, Tensor q, Tensor k, "
            "Tensor v, Tensor out, Tensor lse, bool causal) -> Tensor")
+# sliding-window causal attention: ops of their own, so that whatever
+# matches the schemas above (lowering passes, presets, the ring-attention
+# rewrite) keeps matching exactly what it did
+lib.define("flash_attention_swa(Tensor q, Tensor k, Tensor v, int window) "
+           "-> (Tensor, Tensor)")
+lib.define("flash_attention_swa_bwd(Tensor grad, Tensor q, Tensor k, "
+           "Tensor v, Tensor out, Tensor lse, int window) "
+           "-> (Tensor, Tensor, Tensor)")
 
 
 def _group(q, k, v):
@@ -65,15 +80,33 @@ def _reduce_kv(d, G, dtype):
     return d.to(dtype)
 
 
-def _math_fwd(q, k, v, causal):
-    # q: [B, H, S, D]; k,v: [B, Hkv, T, D]
+def _mask(S, T, window, device):
+    """Causal mask [S, T], True = visible; with a window the band
+    i - window < j <= i."""
+    mask = torch.ones(S, T, dtype=torch.bool, device=device).tril()
+    if window is not None:
+        mask = mask & ~torch.ones(S, T, dtype=torch.bool,
+                                  device=device).tril(-window)
+    return mask
+
+
+def _check_window(q, k, window):
+    if window < 1:
+        raise ValueError(f"flash_attention_swa: window must be >= 1, got "
+                         f"{window}")
+    if q.shape[-2] != k.shape[-2]:
+        raise ValueError("flash_attention_swa: self-attention only, got "
+                         f"Sq {q.shape[-2]} and Sk {k.shape[-2]}")
+
+
+def _math_fwd(q, k, v, causal, window=None):
+    # q: [B, H, S, D]; k,v: [B, Hkv, T, D]; a window implies causal
     G = _group(q, k, v)
     k, v = _expand_kv(k, G), _expand_kv(v, G)
     scale = 1.0 / math.sqrt(q.shape[-1])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
-        S, T = s.shape[-2], s.shape[-1]
-        mask = torch.ones(S, T, dtype=torch.bool, device=s.device).tril()
+        mask = _mask(s.shape[-2], s.shape[-1], window, s.device)
         s = s.masked_fill(~mask, float("-inf"))
     lse = torch.logsumexp(s, dim=-1)
     p = torch.exp(s - lse.unsqueeze(-1))
@@ -81,15 +114,14 @@ def _math_fwd(q, k, v, causal):
     return out, lse
 
 
-def _math_bwd(grad, q, k, v, out, lse, causal):
+def _math_bwd(grad, q, k, v, out, lse, causal, window=None):
     G = _group(q, k, v)
     kdt, vdt = k.dtype, v.dtype
     k, v = _expand_kv(k, G), _expand_kv(v, G)
     scale = 1.0 / math.sqrt(q.shape[-1])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
-        S, T = s.shape[-2], s.shape[-1]
-        mask = torch.ones(S, T, dtype=torch.bool, device=s.device).tril()
+        mask = _mask(s.shape[-2], s.shape[-1], window, s.device)
         s = s.masked_fill(~mask, float("-inf"))
     p = torch.exp(s - lse.unsqueeze(-1).float())
     gradf = grad.float()
@@ -144,6 +176,36 @@ def _bwd_cuda(grad, q, k, v, out, lse, causal):
     return _math_bwd(grad, q, k, v, out, lse, causal)
 
 
+def _swa_fwd_cpu(q, k, v, window):
+    _check_window(q, k, window)
+    return _math_fwd(q, k, v, True, window)
+
+
+def _swa_fwd_cuda(q, k, v, window):
+    _check_window(q, k, window)
+    ext = load_extension()
+    if ext is not None and _kernel_ok(q, k, v):
+        return ext.flash_attn_fwd(q, k, v, True, window)
+    from . import require_hip_ops
+    if _kernel_ok(q, k, v):
+        require_hip_ops()   # raises when the extension should exist
+    return _math_fwd(q, k, v, True, window)
+
+
+def _swa_bwd_cpu(grad, q, k, v, out, lse, window):
+    _check_window(q, k, window)
+    return _math_bwd(grad, q, k, v, out, lse, True, window)
+
+
+def _swa_bwd_cuda(grad, q, k, v, out, lse, window):
+    _check_window(q, k, window)
+    ext = load_extension()
+    if ext is not None and _kernel_ok(q, k, v):
+        return ext.flash_attn_bwd(grad, q, k, v, out.contiguous(),
+                                  lse.contiguous(), True, window)
+    return _math_bwd(grad, q, k, v, out, lse, True, window)
+
+
 def _pack3(dq, dk, dv):
     B, _, S, D = dq.shape
     return torch.cat([d.transpose(1, 2).reshape(B, S, d.shape[1] * D)
@@ -168,6 +230,10 @@ lib.impl("flash_attention_bwd", _bwd_cpu, "CPU")
 lib.impl("flash_attention_bwd", _bwd_cuda, "CUDA")
 lib.impl("flash_attention_bwd_pack", _bwd_pack_cpu, "CPU")
 lib.impl("flash_attention_bwd_pack", _bwd_pack_cuda, "CUDA")
+lib.impl("flash_attention_swa", _swa_fwd_cpu, "CPU")
+lib.impl("flash_attention_swa", _swa_fwd_cuda, "CUDA")
+lib.impl("flash_attention_swa_bwd", _swa_bwd_cpu, "CPU")
+lib.impl("flash_attention_swa_bwd", _swa_bwd_cuda, "CUDA")
 
 
 @torch.library.register_fake("easydist_amd::flash_attention")
@@ -191,6 +257,16 @@ def _fabp_fake(grad, q, k, v, out, lse, causal):
     return q.new_empty((B, S, (H + 2 * k.shape[1]) * D))
 
 
+@torch.library.register_fake("easydist_amd::flash_attention_swa")
+def _swa_fake(q, k, v, window):
+    return _fa_fake(q, k, v, True)
+
+
+@torch.library.register_fake("easydist_amd::flash_attention_swa_bwd")
+def _swab_fake(grad, q, k, v, out, lse, window):
+    return _fab_fake(grad, q, k, v, out, lse, True)
+
+
 def _fa_backward(ctx, grad_out, grad_lse):
     q, k, v, out, lse = ctx.saved_tensors
     dq, dk, dv = torch.ops.easydist_amd.flash_attention_bwd(
@@ -209,6 +285,36 @@ torch.library.register_autograd("easydist_amd::flash_attention", _fa_backward,
                                 setup_context=_fa_setup_ctx)
 
 
-def scaled_dot_product_attention(q, k, v, causal: bool = True):
+def _swa_backward(ctx, grad_out, grad_lse):
+    q, k, v, out, lse = ctx.saved_tensors
+    dq, dk, dv = torch.ops.easydist_amd.flash_attention_swa_bwd(
+        grad_out, q, k, v, out, lse, ctx.window)
+    return dq, dk, dv, None
+
+
+def _swa_setup_ctx(ctx, inputs, output):
+    q, k, v, window = inputs
+    out, lse = output
+    ctx.save_for_backward(q, k, v, out, lse)
+    ctx.window = window
+
+
+torch.library.register_autograd("easydist_amd::flash_attention_swa",
+                                _swa_backward, setup_context=_swa_setup_ctx)
+
+
+def scaled_dot_product_attention(q, k, v, causal: bool = True,
+                                 window: Optional[int] = None):
+    """window = W: sliding-window causal attention, row i attends keys
+    i - W + 1 .. i (flash_attention_swa); it needs causal=True."""
+    if window is not None:
+        if not causal:
+            raise ValueError("scaled_dot_product_attention: a window needs "
+                             "causal=True")
+        if window < 1:
+            raise ValueError("scaled_dot_product_attention: window must be "
+                             f">= 1, got {window}")
+        out, _ = torch.ops.easydist_amd.flash_attention_swa(q, k, v, window)
+        return out
     out, _ = torch.ops.easydist_amd.flash_attention(q, k, v, causal)
     return out

@@ -135,9 +135,10 @@ template <int D, bool TR, int NW = 8> constexpr int dkv_lds_elems() {
 // probabilities are exact zeros and 0 * (a copied row) is 0; a q or key
 // row >= S that a wave owns computes what row S - 1 computes, an MFMA
 // keeps rows apart, and such accumulator rows are never stored.  No q row
-// < S can be fully masked (under the causal mask row i always sees key
-// i), so the -1e30 sentinel and 1 / l_run need no special case here
-// either: do not add one.  Every wave, including one whose 16 rows are all
+// < S can be fully masked over the whole loop (under the causal mask, with
+// or without a window, row i always sees key i), so 1 / l_run needs no
+// special case here either: do not add one.  Within ONE tile a row can be,
+// and under WIN before it has seen any key: the forward's m_ref handles it.  Every wave, including one whose 16 rows are all
 // >= S, walks the same block-uniform tile loop and so reaches every
 // __syncthreads(), with EXEC all ones at every transposed read.
 template <bool RAGGED>
@@ -156,6 +157,48 @@ DEVINL int rag_row(int row, int S) {
 // dk and dv are rounded to bf16 once, with no atomics and no second pass.
 // GQA exists in the default forms only (fwd and dq TR = 1, dkv SW = 0 and
 // TR = ATTN_TR_DKV(D, NW)), like RAGGED.
+
+// ---- WIN: sliding-window causal attention -----------------------------------
+// Query row i attends keys j with i - W < j <= i: W keys, itself included
+// (Mistral's sliding_window = W).  WIN is a template bool and W a runtime
+// int, the last kernel argument.  WIN = false is the code as it was
+// measured: W is never read there, the first tile stays the literal 0 and
+// every added test folds away, so the compiler emits the same instructions
+// as before the parameter existed.  WIN = true is always causal, and the
+// launch code picks it only for W < S: W >= S is plain causal attention and
+// runs the causal kernels.  A runtime W costs one SGPR, and band_ok keeps a
+// masked element at one compare; a template W would need an instantiation
+// per window.
+// WIN exists in the default forms only, like RAGGED and GQA (fwd and dq
+// TR = 1, dkv SW = 0 and TR = ATTN_TR_DKV(D, NW)), for both dkv geometries
+// and with or without RAGGED and GQA: 8 fwd, 8 dq and 16 dkv instantiations.
+// Their registers are listed in profiles/README.md (Round 12): fwd and dq
+// keep their parents' VGPRs within 6 and nothing spills but the two 8-wave
+// D = 128 GQA dkv kernels (12 and 24 bytes per lane; their parents sit at
+// 254 and 256 VGPRs).
+// The tile loops stay block-uniform and only their bounds move:
+//   fwd, dq: the q block at qb0 walks kv tiles max(0, qb0 - W + 1) / KB up
+//     to the causal end.  The first tile can be odd; the LDS buffer of tile
+//     t is t & 1 throughout, in the prologue too.
+//   dkv: the key block at kb0 walks q tiles from kb0 to
+//     min(S, kb0 + KBLK - 1 + W), per query head under GQA.
+// A fwd or dq wave whose 16 rows lie wholly outside a tile's band skips the
+// MFMA work and still reaches every barrier (dkv keeps its causal skip only:
+// the q ranges of a block's waves differ by less than one tile); only tiles
+// that an edge of the band cuts take the per-element compares.  In the backward kernels P is recomputed
+// from lse and a masked entry is an exact zero, as under the causal mask.
+// In the forward a tile can be fully masked for some rows of a wave and be
+// the first tile those rows meet (W = 16 at a 64-key tile boundary): see
+// the note at m_ref there.
+
+// WIN only: may q row `qrow` attend key `key`?  The causal and the left-edge
+// test as one unsigned compare, 0 <= qrow - key < W, so a masked element
+// costs the window kernels what it costs the causal ones.  The WIN = false
+// mask sites keep their own spelling under `if constexpr`: routed through a
+// helper they compiled to selects where they had been branches.
+DEVINL bool band_ok(int key, int qrow, int W) {
+  return (unsigned)(qrow - key) < (unsigned)W;
+}
 
 // ---- shared pieces of the swapped-operand (S^T) form ----------------------
 // pack a C-layout f32 fragment row-pair into bf16x2 words
@@ -204,7 +247,8 @@ DEVINL bf16x8v swp_butterfly(const unsigned pk[][2], int ks, int fg) {
 // butterfly above instead of an LDS strip round-trip.  The un-swapped
 // strip form, a 256-row (two fragments per wave) block and direct-from-L2
 // K reads were all A/B'd on hardware and lost (profiles/README.md).
-template <int D, bool TR, bool RAGGED = false, bool GQA = false>
+template <int D, bool TR, bool RAGGED = false, bool GQA = false,
+          bool WIN = false>
 __global__ void
 // waves/SIMD floor.  The aligned D = 64 kernel fits 5 (96 VGPRs); the
 // clamped row index costs the ragged one 4 more, so it runs at 4: a floor
@@ -215,7 +259,8 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                  float* __restrict__ LSE, int B, int H, int S, bool causal,
                  float scale,
                  long qsb, long qsh, long qss, long ksb, long ksh, long kss,
-                 long vsb, long vsh, long vss, int map_mode, int G) {
+                 long vsb, long vsh, long vss, int map_mode, int G, int W) {
+  static_assert(!WIN || TR, "the window kernels are instantiated for TR = 1");
   // grid: 1-D, ceil(S/QBLK) * B*H workgroups placed by attn_block_map
   // (attn_block_map.h); 8 waves of one 16-row fragment each.  The round-1
   // 4-wave/256-thread form ran ONE wave per SIMD (110 KB LDS) — every
@@ -283,6 +328,8 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
 
   const int kv_end = causal ? min(S, qb0 + QBLK) : S;
   const int n_tiles = (kv_end + KB - 1) / KB;
+  // first tile: the one that holds the first key of the block's first row
+  const int t_beg = WIN ? max(0, qb0 - W + 1) / KB : 0;
   constexpr int PF = TILE_K / (NTHR * 8);    // 16B vectors per thread
   stage_t<TR> kreg[PF], vreg[PF];
 
@@ -315,11 +362,11 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
     }
   };
 
-  load_tile(0);
-  store_tile(0);
+  load_tile(t_beg);
+  store_tile(t_beg);
   __syncthreads();
 
-  for (int t = 0; t < n_tiles; ++t) {
+  for (int t = t_beg; t < n_tiles; ++t) {
     const int kv0 = t * KB;
     const bf16* k_lds = smem_b + (t & 1) * (TILE_K + TILE_VT);
     const bf16* vt_lds = k_lds + TILE_K;
@@ -328,8 +375,10 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
 
     // a 128-row block spans 8 waves: tiles strictly above this wave's
     // causal diagonal are all-masked — skip the compute (NOT the
-    // barriers: every wave still arrives at __syncthreads)
-    const bool wave_active = !(causal && kv0 > qr0 + 15);
+    // barriers: every wave still arrives at __syncthreads); under WIN
+    // so are tiles wholly left of the window of the wave's first row
+    const bool wave_active = !(causal && kv0 > qr0 + 15) &&
+                             !(WIN && kv0 + KB - 1 <= qr0 - W);
     if (wave_active) {
       // ---- S^T = K Q^T: lane col = qrow, regs = 16 keys ---------------
       f32x4 s_acc[KB / 16];
@@ -348,9 +397,10 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
       __builtin_amdgcn_s_setprio(0);
       // ---- online softmax ---------------------------------------------
       // interior tiles (fully below the causal diagonal, fully in-range)
-      // skip the per-element mask compares — most tiles at long S
+      // skip the per-element mask compares — most tiles at long S; under
+      // WIN a tile that the left edge of this row's window cuts has them
       const bool need_mask = (causal && kv0 + KB - 1 > qrow)
-                             || (kv0 + KB > S);
+                             || (kv0 + KB > S) || (WIN && kv0 <= qrow - W);
       float mx = -1e30f;
       if (need_mask) {
         #pragma unroll
@@ -359,7 +409,11 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
           for (int r = 0; r < 4; ++r) {
             int kcol = kv0 + j * 16 + 4 * fg + r;
             float sv = s_acc[j][r];        // already scale*log2e scaled
-            if ((causal && kcol > qrow) || kcol >= S) sv = -1e30f;
+            if constexpr (WIN) {
+              if (!band_ok(kcol, qrow, W) || kcol >= S) sv = -1e30f;
+            } else {
+              if ((causal && kcol > qrow) || kcol >= S) sv = -1e30f;
+            }
             s_acc[j][r] = sv;
             mx = fmaxf(mx, sv);
           }
@@ -372,12 +426,24 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
       mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
       mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
       float m_new = fmaxf(m_run, mx);
+      // Under the causal mask alone a row's first tile holds key 0, so m_new
+      // is a real score from there on and a masked entry gives
+      // exp2(-1e30 - m_new) = 0.  Under WIN the tiles left of a row's
+      // window can come first and be masked whole for that row while other
+      // rows of the wave need them: m_new is still the sentinel there and
+      // exp2(-1e30 - -1e30) would be 1 for every masked key.  Such a row
+      // subtracts 0 instead: its probabilities are exact zeros, l_run and
+      // o_acc stay 0, and alpha = exp2(0) = 1 scales zeros.  At the row's
+      // first real tile alpha = exp2(-1e30 - m_new) = 0 as for any first
+      // tile.  Every q row < S sees key i in some tile, so 1 / l_run needs
+      // no special case.
+      const float m_ref = (WIN && m_new == -1e30f) ? 0.f : m_new;
       float psum = 0.f;
       #pragma unroll
       for (int j = 0; j < KB / 16; ++j)
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float pp = __builtin_amdgcn_exp2f(s_acc[j][r] - m_new);
+          float pp = __builtin_amdgcn_exp2f(s_acc[j][r] - m_ref);
           s_acc[j][r] = pp;
           psum += pp;
         }
@@ -527,16 +593,37 @@ static inline dim3 ed_attn_grid(long nblk, long nbh, const char* who) {
   return dim3((unsigned)(nblk * nbh));
 }
 
-std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
-                                                  const at::Tensor& k_,
-                                                  const at::Tensor& v_,
-                                                  bool causal) {
+// The window of one launch: 0 = none.  A window needs causal, W >= 1, and
+// W >= S is plain causal attention: it runs the causal kernels.
+static inline int ed_attn_window(std::optional<int64_t> window, bool causal,
+                                 long S, const char* who) {
+  if (!window.has_value()) return 0;
+  TORCH_CHECK(*window >= 1, who, ": window must be >= 1, got ", *window);
+  TORCH_CHECK(causal, who, ": a window needs causal attention");
+  return *window >= S ? 0 : (int)*window;
+}
+
+// The window instantiations: default forms only (TR = 1)
+using fwd_kern_t = decltype(&flash_fwd_kernel<64, true>);
+template <int D>
+static fwd_kern_t ed_fwd_pick_win(bool ragged, bool gqa) {
+  if (gqa)
+    return ragged ? flash_fwd_kernel<D, true, true, true, true>
+                  : flash_fwd_kernel<D, true, false, true, true>;
+  return ragged ? flash_fwd_kernel<D, true, true, false, true>
+                : flash_fwd_kernel<D, true, false, false, true>;
+}
+
+std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(
+    const at::Tensor& q_, const at::Tensor& k_, const at::Tensor& v_,
+    bool causal, std::optional<int64_t> window) {
   auto q = ed_attn_arg(q_), k = ed_attn_arg(k_), v = ed_attn_arg(v_);
   const int G = ed_attn_group(q, k, v, "flash_attn_fwd");
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "flash_attn_fwd: D in {64,128}");
   TORCH_CHECK(S >= 1, "flash_attn_fwd: S >= 1");
   const bool ragged = S % (2 * QB) != 0;
+  const int W = ed_attn_window(window, causal, S, "flash_attn_fwd");
   auto out = at::empty({B, H, S, D}, q.options());
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -545,7 +632,8 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
   const int map_mode = ed_attn_map_mode();
   // LDS bytes -> workgroups per 160-KiB CU, D = 64 / 128:
   //   TR = 0: 48 / 80 KiB -> 3 / 2;  TR = 1: 32 / 64 KiB -> 5 / 2
-  const bool tr = (ragged || G > 1) ? ATTN_TR_FWD : ed_attn_tr(ATTN_TR_FWD);
+  const bool tr = (ragged || G > 1 || W) ? ATTN_TR_FWD
+                                         : ed_attn_tr(ATTN_TR_FWD);
   static_assert(ATTN_TR_FWD == 1 && ATTN_TR_DQ == 1,
                 "the ragged and GQA fwd and dq kernels are instantiated "
                 "for TR = 1");
@@ -566,13 +654,16 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
                   : flash_fwd_kernel<64, true, false, true>)
         : (ragged ? flash_fwd_kernel<128, true, true, true>
                   : flash_fwd_kernel<128, true, false, true>);
+  if (W)
+    kern = (D == 64) ? ed_fwd_pick_win<64>(ragged, G > 1)
+                     : ed_fwd_pick_win<128>(ragged, G > 1);
   hipLaunchKernelGGL(kern, grid, block, lds, stream,
       (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
       (const bf16*)v.data_ptr(), (bf16*)out.data_ptr(),
       lse.data_ptr<float>(), B, H, S, causal, scale,
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), map_mode, G);
+      v.stride(0), v.stride(1), v.stride(2), map_mode, G, W);
   return {out, lse};
 }
 
@@ -589,7 +680,8 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q_,
 // hold row fr, k-slice fg; C/D lanes hold row 4*fg+r, col fr.
 // ---------------------------------------------------------------------------
 
-template <int D, bool TR, bool RAGGED = false, bool GQA = false>
+template <int D, bool TR, bool RAGGED = false, bool GQA = false,
+          bool WIN = false>
 __global__ void __launch_bounds__(512)
 flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -599,7 +691,8 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     long dsb, long dsh, long dss, long qsb, long qsh,
                     long qss, long ksb, long ksh, long kss, long vsb,
                     long vsh, long vss, long osb, long osh, long oss,
-                    int map_mode, int G) {
+                    int map_mode, int G, int W) {
+  static_assert(!WIN || TR, "the window kernels are instantiated for TR = 1");
   // 8 waves x 16 q rows: two 64-row halves share each staged K/V tile
   // (2x arithmetic intensity vs the 4-wave form) at 6+ waves/SIMD.
   // grid: 1-D, ceil(S/128) * B*H workgroups placed by attn_block_map
@@ -692,15 +785,19 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       }
     }
   };
-  kv_load(0);
-  kv_store(0);
+  // WIN: first tile as in the forward, in the buffer of its parity
+  const int t_beg = WIN ? max(0, qb0 - W + 1) / KB : 0;
+  kv_load(t_beg * KB);
+  kv_store(t_beg & 1);
   __syncthreads();
   const int n_kt = (kv_end + KB - 1) / KB;
-  for (int tt = 0; tt < n_kt; ++tt) {
+  for (int tt = t_beg; tt < n_kt; ++tt) {
     const int kv0 = tt * KB;
     const int bofs = (tt & 1) * DQBUF;
     if (tt + 1 < n_kt) kv_load(kv0 + KB);
-    if (causal && kv0 > qr0 + 15) {
+    // tiles right of the wave's causal diagonal or (WIN) wholly left of
+    // the window of its first row: barriers only
+    if ((causal && kv0 > qr0 + 15) || (WIN && kv0 + KB - 1 <= qr0 - W)) {
       if (tt + 1 < n_kt) kv_store((tt + 1) & 1);
       __syncthreads();
       continue;
@@ -727,15 +824,20 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     }
     // dS = P * (dP - delta) * scale, P = exp(S*scale - lse)
     const bool need_mask = (causal && kv0 + KB - 1 > qrow)
-                           || (kv0 + KB > S);
+                           || (kv0 + KB > S) || (WIN && kv0 <= qrow - W);
     #pragma unroll
     for (int j = 0; j < KB / 16; ++j)
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float p = 0.f;
         int kcol = kv0 + j * 16 + 4 * fg + r;
-        if (!need_mask || (!(causal && kcol > qrow) && kcol < S))
-          p = __expf(s_acc[j][r] * scale - lse_r);
+        if constexpr (WIN) {
+          if (!need_mask || (band_ok(kcol, qrow, W) && kcol < S))
+            p = __expf(s_acc[j][r] * scale - lse_r);
+        } else {
+          if (!need_mask || (!(causal && kcol > qrow) && kcol < S))
+            p = __expf(s_acc[j][r] * scale - lse_r);
+        }
         s_acc[j][r] = p * (dp_acc[j][r] - dlt_r) * scale;
       }
     // dS to the A-operand layout in-register (no strip, no fences)
@@ -791,7 +893,7 @@ template <int D, int NW> constexpr int dkv_waves_per_simd() {
   return NW == 8 ? 2 : (D == 64 ? 3 : 2);
 }
 template <int D, int SW, bool TR, bool RAGGED = false, bool GQA = false,
-          int NW = 8, bool HT = false>
+          int NW = 8, bool HT = false, bool WIN = false>
 __global__ void __launch_bounds__(NW * WAVE, (dkv_waves_per_simd<D, NW>()))
 flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -802,7 +904,8 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      long dsb, long dsh, long dss, long qsb, long qsh,
                      long qss, long ksb, long ksh, long kss, long vsb,
                      long vsh, long vss, long osb, long osh, long oss,
-                     int map_mode, int G) {
+                     int map_mode, int G, int W) {
+  static_assert(!(WIN && SW), "the window runs the strip form only");
   // NW waves x 16 key rows share each staged Q/dO tile (see dq note)
   // grid: 1-D as in dq; kv block 0 is the causal-heavy one here, so the
   // map keeps the index order (heavy_last_index = false)
@@ -838,7 +941,12 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   const float* delta_h = DELTA + (long)bh * (GQA ? G : 1) * S;
 
   const int lane = threadIdx.x % WAVE;
-  const int wave = threadIdx.x / WAVE;
+  // 4-wave WIN: the wave index as a scalar, so that kr0 and the wave's mask
+  // tests live in SGPRs (the GQA window kernels spilled without it; the
+  // 8-wave ones spill more with it)
+  const int wave = (WIN && NW == 4)
+      ? __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE)
+      : threadIdx.x / WAVE;
   const int kr0 = kb0 + wave * 16;          // this wave's first key row
   const int fr = lane & 15;
   const int fg = lane >> 4;
@@ -912,7 +1020,9 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   // th = tt % n_qh of that head (kept as a counter, no division).  The
   // buffer parity is that of tt, so it runs on across a head switch, and
   // the trip count is block-uniform: every wave reaches every barrier.
-  const int n_qh = (S - q_start + QB - 1) / QB;    // tiles per query head
+  // WIN: the block's last key kb0 + KBLK - 1 is seen by W rows from itself on
+  const int q_end = WIN ? min(S, kb0 + KBLK - 1 + W) : S;
+  const int n_qh = (q_end - q_start + QB - 1) / QB;   // tiles per query head
   const int n_qt = GQA ? G * n_qh : n_qh;
   int th = 0;
   for (int tt = 0; tt < n_qt; ++tt) {
@@ -952,7 +1062,8 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     // full-tile walk below.  The strip keeps its 16 x QB layout; half hh
     // owns its columns 32 hh .. 32 hh + 31, so the halves never share an
     // element and no fence separates them.
-    const bool need_mask = (causal && kr0 + 15 > q0) || (q0 + QB > S);
+    const bool need_mask = (causal && kr0 + 15 > q0) || (q0 + QB > S) ||
+                           (WIN && q0 + QB - 1 >= kr0 + W);
     #pragma unroll
     for (int hh = 0; hh < QB / 32; ++hh) {
       f32x4 st_acc[2], dpt_acc[2];
@@ -983,8 +1094,13 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
         for (int r = 0; r < 4; ++r) {
           int krow = kr0 + 4 * fg + r;
           float p = 0.f;
-          if (!need_mask || (!(causal && krow > qcol) && qcol < S))
-            p = __expf(st_acc[jj][r] * scale - l);
+          if constexpr (WIN) {
+            if (!need_mask || (band_ok(krow, qcol, W) && qcol < S))
+              p = __expf(st_acc[jj][r] * scale - l);
+          } else {
+            if (!need_mask || (!(causal && krow > qcol) && qcol < S))
+              p = __expf(st_acc[jj][r] * scale - l);
+          }
           st_acc[jj][r] = p;
           s_lds[lsw((4 * fg + r) * QB + j * 16 + fr)] = f2bf(p);
         }
@@ -1064,7 +1180,8 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     }
     // P^T = exp(S^T*scale - lse[qcol]); dS^T = P^T (dP^T - delta[qcol]) scale
     bf16x8v ptf[QB / 32];
-    const bool need_mask = (causal && kr0 + 15 > q0) || (q0 + QB > S);
+    const bool need_mask = (causal && kr0 + 15 > q0) || (q0 + QB > S) ||
+                           (WIN && q0 + QB - 1 >= kr0 + W);
     if (SW) {
       const int krow = kr0 + fr;             // this lane's key row
       // the 4 lse values a lane needs per j are CONSECUTIVE (4*fg+r):
@@ -1101,8 +1218,13 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
         for (int r = 0; r < 4; ++r) {
           int krow = kr0 + 4 * fg + r;
           float p = 0.f;
-          if (!(causal && krow > qcol) && qcol < S)
-            p = __expf(st_acc[j][r] * scale - l);
+          if constexpr (WIN) {
+            if (band_ok(krow, qcol, W) && qcol < S)
+              p = __expf(st_acc[j][r] * scale - l);
+          } else {
+            if (!(causal && krow > qcol) && qcol < S)
+              p = __expf(st_acc[j][r] * scale - l);
+          }
           st_acc[j][r] = p;
           s_lds[lsw((4 * fg + r) * QB + j * 16 + fr)] = f2bf(p);
         }
@@ -1211,18 +1333,41 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   }
 }
 
+// The dq window instantiations, as ed_fwd_pick_win
+using dq_kern_t = decltype(&flash_bwd_dq_kernel<64, true>);
+template <int D>
+static dq_kern_t ed_dq_pick_win(bool ragged, bool gqa) {
+  if (gqa)
+    return ragged ? flash_bwd_dq_kernel<D, true, true, true, true>
+                  : flash_bwd_dq_kernel<D, true, false, true, true>;
+  return ragged ? flash_bwd_dq_kernel<D, true, true, false, true>
+                : flash_bwd_dq_kernel<D, true, false, false, true>;
+}
+
 // The dkv instantiation and its LDS bytes for one launch.  sw and tr are
-// the A/B knobs and apply to the aligned MHA shapes only; ragged S and GQA
-// run the strip form in the geometry's default TR.  The half-tile loop is
+// the A/B knobs and apply to the aligned MHA shapes only; ragged S, GQA and
+// a window run the strip form in the geometry's default TR.  The half-tile loop is
 // the 4-wave geometry's strip form.
 using dkv_kern_t = decltype(&flash_bwd_dkv_kernel<64, 0, false>);
 struct DkvLaunch { dkv_kern_t kern; size_t lds; };
 template <int D, int NW>
-static DkvLaunch ed_dkv_pick(bool sw, bool tr, bool ragged, bool gqa) {
+static DkvLaunch ed_dkv_pick(bool sw, bool tr, bool ragged, bool gqa,
+                             bool win) {
   constexpr bool HT = NW == 4;
   constexpr bool TRD = ATTN_TR_DKV(D, NW);
   constexpr size_t L0 = sizeof(bf16) * dkv_lds_elems<D, false, NW>();
   constexpr size_t L1 = sizeof(bf16) * dkv_lds_elems<D, true, NW>();
+  if (win) {
+    if (gqa)
+      return {ragged
+                  ? flash_bwd_dkv_kernel<D, 0, TRD, true, true, NW, HT, true>
+                  : flash_bwd_dkv_kernel<D, 0, TRD, false, true, NW, HT, true>,
+              TRD ? L1 : L0};
+    return {ragged
+                ? flash_bwd_dkv_kernel<D, 0, TRD, true, false, NW, HT, true>
+                : flash_bwd_dkv_kernel<D, 0, TRD, false, false, NW, HT, true>,
+            TRD ? L1 : L0};
+  }
   if (gqa)
     return {ragged ? flash_bwd_dkv_kernel<D, 0, TRD, true, true, NW, HT>
                    : flash_bwd_dkv_kernel<D, 0, TRD, false, true, NW, HT>,
@@ -1272,7 +1417,8 @@ static void
 flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
                       const at::Tensor& k_, const at::Tensor& v_,
                       const at::Tensor& out, const at::Tensor& lse,
-                      bool causal, bf16* dq_p, bf16* dk_p, bf16* dv_p,
+                      bool causal, std::optional<int64_t> window,
+                      bf16* dq_p, bf16* dk_p, bf16* dv_p,
                       long osb, long kosb, long osh, long oss) {
   // osb: batch stride of dq ([.., H, ..]); kosb: that of dk and dv
   // ([.., Hkv, ..]); head and row strides are common to the three
@@ -1288,6 +1434,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   TORCH_CHECK(D == 64 || D == 128, "flash_attn_bwd: D in {64,128}");
   TORCH_CHECK(S >= 1, "flash_attn_bwd: S >= 1");
   const bool ragged = S % (2 * QB) != 0;
+  const int W = ed_attn_window(window, causal, S, "flash_attn_bwd");
   // delta = rowsum(dO * O), fp32 — one fused bf16 pass
   auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   {
@@ -1311,7 +1458,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   //   dkv (Q+dO+Q^T+dO^T, or Q+dO under TR), double-buffered, + strips:
   //     8 waves: TR = 0: 80 / 144 KiB -> 2 / 1;  TR = 1: 48 / 80 KiB -> 3 / 2
   //     4 waves: TR = 0: 72 / 136 KiB -> 2 / 1;  TR = 1: 40 / 72 KiB -> 4 / 2
-  const bool dflt = ragged || G > 1;   // default forms only
+  const bool dflt = ragged || G > 1 || W;   // default forms only
   const bool tr_q = dflt ? ATTN_TR_DQ : ed_attn_tr(ATTN_TR_DQ);
   size_t lds = sizeof(bf16) *
       (D == 64 ? (tr_q ? dq_lds_elems<64, true>() : dq_lds_elems<64, false>())
@@ -1331,6 +1478,9 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
                   : flash_bwd_dq_kernel<64, true, false, true>)
         : (ragged ? flash_bwd_dq_kernel<128, true, true, true>
                   : flash_bwd_dq_kernel<128, true, false, true>);
+  if (W)
+    qkern = (D == 64) ? ed_dq_pick_win<64>(ragged, G > 1)
+                      : ed_dq_pick_win<128>(ragged, G > 1);
   // dkv: one workgroup of nw waves per block of nw * 16 keys of a K/V head
   // (the same grid as dq when nw == 8 and Hkv == H)
   static int swkv = []() {  // dkv butterfly measured SLOWER than the
@@ -1341,10 +1491,10 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   const bool tr_d = nw == 4 ? ATTN_TR_DKV(D, 4) : ATTN_TR_DKV(D, 8);
   const bool tr_kv = dflt ? tr_d : ed_attn_tr(tr_d);
   const DkvLaunch kv = (D == 64)
-      ? (nw == 4 ? ed_dkv_pick<64, 4>(swkv, tr_kv, ragged, G > 1)
-                 : ed_dkv_pick<64, 8>(swkv, tr_kv, ragged, G > 1))
-      : (nw == 4 ? ed_dkv_pick<128, 4>(swkv, tr_kv, ragged, G > 1)
-                 : ed_dkv_pick<128, 8>(swkv, tr_kv, ragged, G > 1));
+      ? (nw == 4 ? ed_dkv_pick<64, 4>(swkv, tr_kv, ragged, G > 1, W)
+                 : ed_dkv_pick<64, 8>(swkv, tr_kv, ragged, G > 1, W))
+      : (nw == 4 ? ed_dkv_pick<128, 4>(swkv, tr_kv, ragged, G > 1, W)
+                 : ed_dkv_pick<128, 8>(swkv, tr_kv, ragged, G > 1, W));
   dim3 grid_kv = ed_attn_grid((S + nw * 16 - 1) / (nw * 16),
                               (long)B * (H / G), "flash_attn_bwd");
   dim3 block_kv(nw * WAVE);
@@ -1356,7 +1506,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       grad.stride(0), grad.stride(1), grad.stride(2),
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode, G);
+      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode, G, W);
   hipLaunchKernelGGL(kv.kern, grid_kv, block_kv, kv.lds, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
@@ -1365,13 +1515,15 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       grad.stride(0), grad.stride(1), grad.stride(2),
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), kosb, osh, oss, map_mode, G);
+      v.stride(0), v.stride(1), v.stride(2), kosb, osh, oss, map_mode, G,
+      W);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor>
 flash_attn_bwd(const at::Tensor& grad_, const at::Tensor& q_,
                const at::Tensor& k_, const at::Tensor& v_,
-               const at::Tensor& out, const at::Tensor& lse, bool causal) {
+               const at::Tensor& out, const at::Tensor& lse, bool causal,
+               std::optional<int64_t> window) {
   const int B = q_.size(0), H = q_.size(1), S = q_.size(2), D = q_.size(3);
   auto opts = q_.options();
   auto dq = at::empty({B, H, S, D}, opts);
@@ -1379,7 +1531,7 @@ flash_attn_bwd(const at::Tensor& grad_, const at::Tensor& q_,
   const int Hkv = k_.size(1);          // validated by the launch code
   auto dk = at::empty({B, Hkv, S, D}, opts);
   auto dv = at::empty({B, Hkv, S, D}, opts);
-  flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal,
+  flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal, window,
                         (bf16*)dq.data_ptr(), (bf16*)dk.data_ptr(),
                         (bf16*)dv.data_ptr(),
                         (long)H * S * D, (long)Hkv * S * D, (long)S * D, D);
@@ -1405,7 +1557,7 @@ flash_attn_bwd_pack(const at::Tensor& grad_, const at::Tensor& q_,
   bf16* base = (bf16*)dqkv.data_ptr();
   // dq/dk/dv sections at column offsets 0, H*D, (H+Hkv)*D of the packed
   // rows; per-(b,h,s,d) element strides: osb=S*W, osh=D, oss=W
-  flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal,
+  flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal, std::nullopt,
                         base, base + H * D, base + (H + Hkv) * D,
                         S * W, S * W, D, W);
   return dqkv;

@@ -57,11 +57,13 @@ at::Tensor gelu_bwd_fast(const at::Tensor& g, const at::Tensor& x);
 std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q,
                                                   const at::Tensor& k,
                                                   const at::Tensor& v,
-                                                  bool causal);
+                                                  bool causal,
+                                                  std::optional<int64_t> window);
 std::tuple<at::Tensor, at::Tensor, at::Tensor>
 flash_attn_bwd(const at::Tensor& grad, const at::Tensor& q,
                const at::Tensor& k, const at::Tensor& v,
-               const at::Tensor& out, const at::Tensor& lse, bool causal);
+               const at::Tensor& out, const at::Tensor& lse, bool causal,
+               std::optional<int64_t> window);
 at::Tensor
 flash_attn_bwd_pack(const at::Tensor& grad, const at::Tensor& q,
                     const at::Tensor& k, const at::Tensor& v,
@@ -145,10 +147,13 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
         "-> (Tensor, Tensor)");
   m.def("gelu_fast(Tensor x) -> Tensor");
   m.def("gelu_bwd_fast(Tensor g, Tensor x) -> Tensor");
-  m.def("flash_attn_fwd(Tensor q, Tensor k, Tensor v, bool causal) "
-        "-> (Tensor, Tensor)");
+  // window: sliding-window causal attention, row i sees keys i - window + 1
+  // .. i; unset, the four- and seven-argument calls are what they were
+  m.def("flash_attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, "
+        "int? window=None) -> (Tensor, Tensor)");
   m.def("flash_attn_bwd(Tensor grad, Tensor q, Tensor k, Tensor v, "
-        "Tensor out, Tensor lse, bool causal) -> (Tensor, Tensor, Tensor)");
+        "Tensor out, Tensor lse, bool causal, int? window=None) "
+        "-> (Tensor, Tensor, Tensor)");
   m.def("flash_attn_bwd_pack(Tensor grad, Tensor q, Tensor k, Tensor v, "
         "Tensor out, Tensor lse, bool causal) -> Tensor");
   m.def("rope_qkv(Tensor qkv, Tensor cos, Tensor sin, int n_head, "
