@@ -2,8 +2,8 @@
 
 The compute path of the framework (SURVEY.md §7 phase 5): partitioned hot
 ops in the lowered graph run as gfx950 kernels — MFMA-tiled GEMM, flash
-attention, rotary embeddings, fused SwiGLU, LayerNorm fwd/bwd, fused
-multi-tensor Adam, fused cross-entropy.
+attention, rotary embeddings, fused SwiGLU, MoE routing, LayerNorm fwd/bwd,
+fused multi-tensor Adam, fused cross-entropy.
 Plain large GEMMs go to hipBLASLt via aten (torch.mm); everything listed
 here is a hand kernel.
 

@@ -76,6 +76,20 @@ at::Tensor swiglu_fwd(const at::Tensor& gate, const at::Tensor& up);
 std::tuple<at::Tensor, at::Tensor>
 swiglu_bwd(const at::Tensor& grad, const at::Tensor& gate,
            const at::Tensor& up);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+moe_bins_fwd(const at::Tensor& tokens, const at::Tensor& topi,
+             const at::Tensor& topv, int64_t n_experts, int64_t cap);
+std::tuple<at::Tensor, at::Tensor>
+moe_bins_bwd(const at::Tensor& gbins, const at::Tensor& ggates,
+             const at::Tensor& src, const at::Tensor& valid,
+             int64_t n_tokens, int64_t top_k);
+at::Tensor moe_combine_fwd(const at::Tensor& bins, const at::Tensor& gates,
+                           const at::Tensor& src, const at::Tensor& valid,
+                           int64_t n_tokens, int64_t top_k);
+std::tuple<at::Tensor, at::Tensor>
+moe_combine_bwd(const at::Tensor& gout, const at::Tensor& bins,
+                const at::Tensor& gates, const at::Tensor& src,
+                const at::Tensor& valid, int64_t top_k);
 
 // wrappers adapting std::vector<bool> / TensorList signatures
 static std::tuple<at::Tensor, at::Tensor, at::Tensor>
@@ -161,6 +175,14 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
   m.def("swiglu_fwd(Tensor gate, Tensor up) -> Tensor");
   m.def("swiglu_bwd(Tensor grad, Tensor gate, Tensor up) "
         "-> (Tensor, Tensor)");
+  m.def("moe_bins_fwd(Tensor tokens, Tensor topi, Tensor topv, "
+        "int n_experts, int cap) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("moe_bins_bwd(Tensor gbins, Tensor ggates, Tensor src, Tensor valid, "
+        "int n_tokens, int top_k) -> (Tensor, Tensor)");
+  m.def("moe_combine_fwd(Tensor bins, Tensor gates, Tensor src, "
+        "Tensor valid, int n_tokens, int top_k) -> Tensor");
+  m.def("moe_combine_bwd(Tensor gout, Tensor bins, Tensor gates, Tensor src, "
+        "Tensor valid, int top_k) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
@@ -188,6 +210,10 @@ TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
   m.impl("rope_qkv", rope_qkv);
   m.impl("swiglu_fwd", swiglu_fwd);
   m.impl("swiglu_bwd", swiglu_bwd);
+  m.impl("moe_bins_fwd", moe_bins_fwd);
+  m.impl("moe_bins_bwd", moe_bins_bwd);
+  m.impl("moe_combine_fwd", moe_combine_fwd);
+  m.impl("moe_combine_bwd", moe_combine_bwd);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {}

@@ -32,12 +32,49 @@ cap(N) — true for the benchmark shapes; asserted in the model.
 
 src encoding: src = token_index * K + k  (one field carries both the
 token row and which of its top-k slots the bin holds).
+
+On the GPU the four ops run as hand-written gfx950 kernels
+(csrc/moe_kernels.hip) inside this envelope: tokens, bins, gbins, gout,
+topv, gates and ggates bf16 and contiguous, the row tensors with
+C % 8 == 0, C <= 512 (one 16-byte vector per lane of the wave that owns a
+row) and 16-byte aligned data; topi and src int64 and contiguous,
+valid bool; 1 <= E <= 256, 1 <= K <= 8, N >= 1, N*K and E*cap below 2^31.
+Everything else, the CPU, and EASYDIST_MOE_HIP=0 (read at each call, for
+A/B timing) run the aten functions below.  The kernels' contract:
+
+* bins, gates, src and valid of moe_bins, gbins of moe_combine_bwd and
+  gtopv of moe_bins_bwd are equal (torch.equal) to the aten functions: a
+  stable counting sort by expert gives the slot order of aten's stable
+  argsort.  The one difference in bits: the gbins row of an invalid slot
+  is +0 where aten's gout[0] * 0 * 0 is -0 for a negative gout[0];
+* out of moe_combine, gtokens of moe_bins_bwd and ggates of
+  moe_combine_bwd are the exact formula summed in fp32 in a fixed order
+  (k = 0..K-1; the row dot in a lane's registers, then across the lanes of
+  the row's wave) and rounded to bf16 once: tighter than the aten path,
+  which rounds every partial sum to bf16, and the same bits on every run,
+  where aten's index_add_ adds atomically in whatever order the hardware
+  takes.
+
+No atomics, no zero-fill passes, no host synchronisation: the launches go
+to the current stream with scratch from the torch allocator and record
+into a captured graph.
+
+What does not reach the kernels today.  Rows wider than 512 elements, the
+Mixtral bench shape (C = 4096) among them.  And MoEGPT under
+moe_train_step's bf16 autocast, eager or compiled: autocast runs the
+LayerNorm before the router in fp32, so `tokens`, and `topv` cast to its
+dtype, arrive as fp32, `gates` stays fp32 and `gbins` comes back fp32;
+all four ops then run the aten functions.  A model held in bf16
+(MoELayer(cfg).bfloat16()) with n_embd <= 512 runs the kernels.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
+
+from . import load_extension
 
 lib = torch.library.Library("easydist_amd", "FRAGMENT")
 lib.define("moe_bins(Tensor tokens, Tensor topi, Tensor topv, int n_experts,"
@@ -118,12 +155,119 @@ def _combine_bwd_impl(gout, bins, gates, src, valid, top_k):
     return gbins, ggates
 
 
-for _name, _fn in (("moe_bins", _bins_impl),
-                   ("moe_bins_bwd", _bins_bwd_impl),
-                   ("moe_combine", _combine_impl),
-                   ("moe_combine_bwd", _combine_bwd_impl)):
-    lib.impl(_name, _fn, "CPU")
-    lib.impl(_name, _fn, "CUDA")
+MAX_EXPERTS = 256
+MAX_TOP_K = 8
+MAX_ROW = 512      # elements of a row: 64 lanes of 8
+
+
+def _rows_ok(t, ndim):
+    """A bf16 row tensor the kernels read or write with 16-byte vectors."""
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == ndim
+            and t.is_contiguous() and t.size(-1) % 8 == 0
+            and t.size(-1) <= MAX_ROW and t.data_ptr() % 16 == 0)
+
+
+def _flat_ok(t, dtype, shape):
+    return (t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and tuple(t.shape) == tuple(shape))
+
+
+def _sizes_ok(N, K, E, cap):
+    return (1 <= E <= MAX_EXPERTS and 1 <= K <= MAX_TOP_K and N >= 1
+            and cap >= 1 and N * K < 2 ** 31 and E * cap < 2 ** 31)
+
+
+def _slots_ok(rows, gates, src, valid, n_tokens, top_k):
+    """[E, cap, C] rows with their [E, cap] gates and routing metadata."""
+    if not _rows_ok(rows, 3):
+        return False
+    ec = rows.shape[:2]
+    return (_flat_ok(gates, torch.bfloat16, ec)
+            and _flat_ok(src, torch.long, ec)
+            and _flat_ok(valid, torch.bool, ec)
+            and _sizes_ok(n_tokens, top_k, ec[0], ec[1]))
+
+
+def _bins_kernel_ok(tokens, topi, topv, n_experts, capacity_factor):
+    if not _rows_ok(tokens, 2) or topi.dim() != 2:
+        return False
+    N, K = tokens.shape[0], topi.shape[1]
+    return (_flat_ok(topi, torch.long, (N, K))
+            and _flat_ok(topv, torch.bfloat16, (N, K))
+            and _sizes_ok(N, K, n_experts,
+                          capacity(N, n_experts, K, capacity_factor)))
+
+
+def _bins_bwd_kernel_ok(gbins, ggates, src, valid, tokens_ref, top_k):
+    return _slots_ok(gbins, ggates, src, valid, tokens_ref.shape[0], top_k)
+
+
+def _combine_kernel_ok(bins, gates, src, valid, tokens_ref, top_k):
+    return _slots_ok(bins, gates, src, valid, tokens_ref.shape[0], top_k)
+
+
+def _combine_bwd_kernel_ok(gout, bins, gates, src, valid, top_k):
+    return (_rows_ok(gout, 2) and bins.dim() == 3
+            and gout.shape[1] == bins.shape[2]
+            and _slots_ok(bins, gates, src, valid, gout.shape[0], top_k))
+
+
+def _kernels(ok):
+    """The extension when the call is inside the envelope `ok` and the
+    kernels are not switched off; None sends the call to the aten path.
+    Inside the envelope on a GPU host a missing extension is an error."""
+    if not ok or os.environ.get("EASYDIST_MOE_HIP", "1") == "0":
+        return None
+    ext = load_extension()
+    if ext is None:
+        from . import require_hip_ops
+        require_hip_ops()   # raises when the extension should exist
+    return ext
+
+
+def _bins_cuda(tokens, topi, topv, n_experts, capacity_factor):
+    ext = _kernels(_bins_kernel_ok(tokens, topi, topv, n_experts,
+                                   capacity_factor))
+    if ext is None:
+        return _bins_impl(tokens, topi, topv, n_experts, capacity_factor)
+    cap = capacity(tokens.shape[0], n_experts, topi.shape[1],
+                   capacity_factor)
+    return ext.moe_bins_fwd(tokens, topi, topv, n_experts, cap)
+
+
+def _bins_bwd_cuda(gbins, ggates, src, valid, tokens_ref, top_k):
+    ext = _kernels(_bins_bwd_kernel_ok(gbins, ggates, src, valid,
+                                       tokens_ref, top_k))
+    if ext is None:
+        return _bins_bwd_impl(gbins, ggates, src, valid, tokens_ref, top_k)
+    return ext.moe_bins_bwd(gbins, ggates, src, valid, tokens_ref.shape[0],
+                            top_k)
+
+
+def _combine_cuda(bins, gates, src, valid, tokens_ref, top_k):
+    ext = _kernels(_combine_kernel_ok(bins, gates, src, valid, tokens_ref,
+                                      top_k))
+    if ext is None:
+        return _combine_impl(bins, gates, src, valid, tokens_ref, top_k)
+    return ext.moe_combine_fwd(bins, gates, src, valid, tokens_ref.shape[0],
+                               top_k)
+
+
+def _combine_bwd_cuda(gout, bins, gates, src, valid, top_k):
+    ext = _kernels(_combine_bwd_kernel_ok(gout, bins, gates, src, valid,
+                                          top_k))
+    if ext is None:
+        return _combine_bwd_impl(gout, bins, gates, src, valid, top_k)
+    return ext.moe_combine_bwd(gout, bins, gates, src, valid, top_k)
+
+
+for _name, _cpu, _cuda in (
+        ("moe_bins", _bins_impl, _bins_cuda),
+        ("moe_bins_bwd", _bins_bwd_impl, _bins_bwd_cuda),
+        ("moe_combine", _combine_impl, _combine_cuda),
+        ("moe_combine_bwd", _combine_bwd_impl, _combine_bwd_cuda)):
+    lib.impl(_name, _cpu, "CPU")
+    lib.impl(_name, _cuda, "CUDA")
 
 
 @torch.library.register_fake("easydist_amd::moe_bins")

@@ -22,6 +22,7 @@ SRC = [
     "easydist_amd/ops/csrc/attn_kernels.hip",
     "easydist_amd/ops/csrc/rope_kernels.hip",
     "easydist_amd/ops/csrc/swiglu_kernels.hip",
+    "easydist_amd/ops/csrc/moe_kernels.hip",
 ]
 
 setup(
