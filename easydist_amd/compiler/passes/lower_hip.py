@@ -4,8 +4,8 @@ The autocast'd trace runs LayerNorm in fp32: every norm is wrapped in
 bf16->fp32->bf16 casts (rocprof: ~290 cast kernels + aten layer_norm +
 layer_norm_grad_input per GPT-2 step). This pass rewrites
 ``aten.native_layer_norm(_backward)`` to ``easydist_amd::layer_norm_fwd/
-bwd`` (one-pass Welford / two-pass bwd HIP kernels that take bf16
-directly with fp32 statistics inside), FOLDING the surrounding casts:
+bwd`` (fwd: the mean, then the centred variance; two-pass bwd; HIP kernels
+that take bf16 directly with fp32 statistics), FOLDING the surrounding casts:
 
 * an input that is ``_to_copy(x_bf16, fp32)`` feeds the kernel as x_bf16;
 * a user that is ``_to_copy(out, bf16)`` reads the kernel's bf16 output

@@ -36,6 +36,8 @@ DEVINL void vstore8(float* p, int i, const float* v) {
   for (int u = 0; u < 8; ++u) p[i + u] = v[u];
 }
 
+#define CE_MAX_INIT (-3.402823466e+38f)   // -FLT_MAX
+
 template <typename T>
 __global__ void ce_fwd_kernel(const T* __restrict__ logits,
                               const long* __restrict__ targets,
@@ -48,7 +50,10 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
   const T* lrow = logits + (long)row * V;
   // online max + sumexp; 8-wide vector loads (16B bf16 / 32B fp32 per
   // lane-iteration) keep the 8 TB/s HBM stream coalesced
-  float m = -INFINITY, s = 0.f;
+  // The running max starts at a finite sentinel: with -inf, a lane that has
+  // seen only -inf logits (a masked vocabulary) would take exp(-inf + inf).
+  // Below any finite logit, so finite rows compute what they always did.
+  float m = CE_MAX_INIT, s = 0.f;
   const int V8 = (V / 8) * 8;
   for (int i = lane * 8; i < V8; i += WAVE * 8) {
     float v8[8];

@@ -13,6 +13,78 @@
 #include <cstdlib>
 
 // ---------------------------------------------------------------- fwd -------
+// LayerNorm statistics are two sweeps over the row: the mean, then the mean
+// of the squared deviations from it. E[x^2] - mean^2 in fp32 loses
+// (mean/sigma)^2 of its digits (rstd 8% off on rows of 1000 + randn). A lane
+// keeps its first NORM_REG_V vectors of the row in registers, so for
+// D <= 2048 the row is read once; longer rows re-read their tail.
+//
+// norm_fwd_kernel and add_norm_fwd_kernel must agree bit for bit
+// (tests/test_gpu_norm_fuse.py), so both take every rounding step of the
+// LayerNorm form from the helpers below, compiled with contraction off: the
+// same adds and multiplies in the same order, whatever surrounds the call.
+#define NORM_REG_V 4          // bf16x8 vectors of a row held per lane
+
+// The row sum is taken in fp64: a lane's bf16 values add up exactly there,
+// so the mean is known far beyond fp32 and an element that lies at its
+// row's mean still gets a relatively accurate x - mean.
+DEVINL double ln_vec_sum(const bf16x8& v, double s) {
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) s += (double)bf2f(v.v[j]);
+  return s;
+}
+
+DEVINL double wave_sum_f64(double x) {
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    x += __shfl_down(x, off, WAVE);
+  return __shfl(x, 0, WAVE);
+}
+
+DEVINL float ln_vec_sqdev(const bf16x8& v, float mean, float s) {
+  #pragma clang fp contract(off)
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float d = bf2f(v.v[j]) - mean;
+    const float q = d * d;
+    s += q;
+  }
+  return s;
+}
+
+// mean = sum / D rounded to fp32, which is what is stored, and in *lo what
+// that rounding dropped: out is normalised as (x - mean) - lo, with none of
+// the mean's rounding error in it. lo comes from the exact residual
+// sum - mean * D, so a constant row (sum = c * D) has lo = 0 exactly.
+DEVINL float ln_mean(double sum, int D, double inv_d, float* lo) {
+  const float mean = (float)(sum * inv_d);
+  const double res = __builtin_fma(-(double)mean, (double)D, sum);
+  *lo = (float)(res * inv_d);
+  return mean;
+}
+
+DEVINL float ln_rstd(float sqsum, int D, float eps) {
+  #pragma clang fp contract(off)
+  const float var = sqsum / D;
+  return rsqrtf(var + eps);
+}
+
+// ((x - mean) - lo) * rstd [* w] [+ b], each step rounded on its own
+DEVINL bf16x8 ln_vec_apply(const bf16x8& xv, const bf16x8& wv,
+                           const bf16x8& bv, bool has_w, bool has_b,
+                           float mean, float lo, float rstd) {
+  #pragma clang fp contract(off)
+  bf16x8 ov;
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float f = ((bf2f(xv.v[j]) - mean) - lo) * rstd;
+    if (has_w) f *= bf2f(wv.v[j]);
+    if (has_b) f += bf2f(bv.v[j]);
+    ov.v[j] = f2bf(f);
+  }
+  return ov;
+}
+
 template <typename T, bool RMS>
 __global__ void norm_fwd_kernel(const T* __restrict__ x,
                                 const T* __restrict__ w,
@@ -28,48 +100,62 @@ __global__ void norm_fwd_kernel(const T* __restrict__ x,
   T* orow = out + (long)wave_id * D;
 
   const int VEC = 8;
-  float s1 = 0.f, s2 = 0.f;
-  for (int i = lane * VEC; i < D; i += WAVE * VEC) {
-    bf16x8 xv = *reinterpret_cast<const bf16x8*>(&xrow[i]);
+  const int TAIL0 = NORM_REG_V * WAVE * VEC;   // first column not in registers
+  bf16x8 xr[NORM_REG_V];
+  #pragma unroll
+  for (int k = 0; k < NORM_REG_V; ++k) {
+    const int i = lane * VEC + k * WAVE * VEC;
+    if (i < D) xr[k] = *reinterpret_cast<const bf16x8*>(&xrow[i]);
+  }
+  // 1/D does not wait for the row: the fp64 divide overlaps the loads
+  const double inv_d = 1.0 / (double)D;
+  float mean = 0.f, mean_lo = 0.f;
+  if (!RMS) {
+    double s1 = 0.0;
     #pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float f = bf2f(xv.v[j]);
-      s1 += f;
-      s2 += f * f;
-    }
+    for (int k = 0; k < NORM_REG_V; ++k)
+      if (lane * VEC + k * WAVE * VEC < D) s1 = ln_vec_sum(xr[k], s1);
+    for (int i = TAIL0 + lane * VEC; i < D; i += WAVE * VEC)
+      s1 = ln_vec_sum(*reinterpret_cast<const bf16x8*>(&xrow[i]), s1);
+    mean = ln_mean(wave_sum_f64(s1), D, inv_d, &mean_lo);
   }
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  float mean, rstd;
-  if (RMS) {
-    mean = 0.f;
-    rstd = rsqrtf(s2 / D + eps);
-  } else {
-    mean = s1 / D;
-    rstd = rsqrtf(fmaxf(s2 / D - mean * mean, 0.f) + eps);
-  }
+  // RMS: deviations from 0, the plain sum of squares
+  float s2 = 0.f;
+  #pragma unroll
+  for (int k = 0; k < NORM_REG_V; ++k)
+    if (lane * VEC + k * WAVE * VEC < D) s2 = ln_vec_sqdev(xr[k], mean, s2);
+  for (int i = TAIL0 + lane * VEC; i < D; i += WAVE * VEC)
+    s2 = ln_vec_sqdev(*reinterpret_cast<const bf16x8*>(&xrow[i]), mean, s2);
+  const float rstd = ln_rstd(wave_sum(s2), D, eps);
   if (lane == 0) {
     if (!RMS) mean_out[wave_id] = mean;
     rstd_out[wave_id] = rstd;
   }
-  for (int i = lane * VEC; i < D; i += WAVE * VEC) {
-    bf16x8 xv = *reinterpret_cast<const bf16x8*>(&xrow[i]);
-    bf16x8 ov;
+  #pragma unroll
+  for (int k = 0; k < NORM_REG_V; ++k) {
+    const int i = lane * VEC + k * WAVE * VEC;
+    if (i < D) {
+      bf16x8 wv, bv;
+      if (w) wv = *reinterpret_cast<const bf16x8*>(&w[i]);
+      if (b) bv = *reinterpret_cast<const bf16x8*>(&b[i]);
+      *reinterpret_cast<bf16x8*>(&orow[i]) =
+          ln_vec_apply(xr[k], wv, bv, w != nullptr, b != nullptr, mean,
+                       mean_lo, rstd);
+    }
+  }
+  for (int i = TAIL0 + lane * VEC; i < D; i += WAVE * VEC) {
+    const bf16x8 xv = *reinterpret_cast<const bf16x8*>(&xrow[i]);
     bf16x8 wv, bv;
     if (w) wv = *reinterpret_cast<const bf16x8*>(&w[i]);
     if (b) bv = *reinterpret_cast<const bf16x8*>(&b[i]);
-    #pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float f = (bf2f(xv.v[j]) - mean) * rstd;
-      if (w) f *= bf2f(wv.v[j]);
-      if (b) f += bf2f(bv.v[j]);
-      ov.v[j] = f2bf(f);
-    }
-    *reinterpret_cast<bf16x8*>(&orow[i]) = ov;
+    *reinterpret_cast<bf16x8*>(&orow[i]) =
+        ln_vec_apply(xv, wv, bv, w != nullptr, b != nullptr, mean, mean_lo,
+                     rstd);
   }
 }
 
-// fp32 variant
+// fp32 variant: the same two sweeps, the row re-read from memory (L2) each
+// time
 template <bool RMS>
 __global__ void norm_fwd_kernel_f32(const float* __restrict__ x,
                                     const float* __restrict__ w,
@@ -84,22 +170,24 @@ __global__ void norm_fwd_kernel_f32(const float* __restrict__ x,
   const float* xrow = x + (long)wave_id * D;
   float* orow = out + (long)wave_id * D;
   const int VEC = 4;
-  float s1 = 0.f, s2 = 0.f;
+  float mean = 0.f;
+  if (!RMS) {
+    float s1 = 0.f;
+    for (int i = lane * VEC; i < D; i += WAVE * VEC) {
+      float4 xv = *reinterpret_cast<const float4*>(&xrow[i]);
+      s1 += xv.x + xv.y + xv.z + xv.w;
+    }
+    mean = wave_sum(s1) / D;
+  }
+  float s2 = 0.f;
   for (int i = lane * VEC; i < D; i += WAVE * VEC) {
     float4 xv = *reinterpret_cast<const float4*>(&xrow[i]);
-    s1 += xv.x + xv.y + xv.z + xv.w;
-    s2 += xv.x * xv.x + xv.y * xv.y + xv.z * xv.z + xv.w * xv.w;
+    const float d0 = xv.x - mean, d1 = xv.y - mean;
+    const float d2 = xv.z - mean, d3 = xv.w - mean;
+    s2 += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
   }
-  s1 = wave_sum(s1);
   s2 = wave_sum(s2);
-  float mean, rstd;
-  if (RMS) {
-    mean = 0.f;
-    rstd = rsqrtf(s2 / D + eps);
-  } else {
-    mean = s1 / D;
-    rstd = rsqrtf(fmaxf(s2 / D - mean * mean, 0.f) + eps);
-  }
+  const float rstd = rsqrtf(s2 / D + eps);
   if (lane == 0) {
     if (!RMS) mean_out[wave_id] = mean;
     rstd_out[wave_id] = rstd;
@@ -299,31 +387,32 @@ add_norm_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b,
       bv[k] = *reinterpret_cast<const bf16x8*>(&b[base + i]);
     }
   }
-  float s1 = 0.f, s2 = 0.f;
   #pragma unroll
   for (int k = 0; k < NV; ++k) {
     const int i = lane * VEC + k * WAVE * VEC;
     if (i < D) {
       #pragma unroll
-      for (int j = 0; j < VEC; ++j) {
+      for (int j = 0; j < VEC; ++j)
         sv[k].v[j] = f2bf(bf2f(av[k].v[j]) + bf2f(bv[k].v[j]));
-        float f = bf2f(sv[k].v[j]);
-        s1 += f;
-        s2 += f * f;
-      }
       *reinterpret_cast<bf16x8*>(&sum[base + i]) = sv[k];
     }
   }
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  float mean, rstd;
-  if (RMS) {
-    mean = 0.f;
-    rstd = rsqrtf(s2 / D + eps);
-  } else {
-    mean = s1 / D;
-    rstd = rsqrtf(fmaxf(__builtin_fmaf(-mean, mean, s2 / D), 0.f) + eps);
+  // the sweeps of norm_fwd_kernel, over the registers that hold the sum
+  // 1/D does not wait for the row: the fp64 divide overlaps the loads
+  const double inv_d = 1.0 / (double)D;
+  float mean = 0.f, mean_lo = 0.f;
+  if (!RMS) {
+    double s1 = 0.0;
+    #pragma unroll
+    for (int k = 0; k < NV; ++k)
+      if (lane * VEC + k * WAVE * VEC < D) s1 = ln_vec_sum(sv[k], s1);
+    mean = ln_mean(wave_sum_f64(s1), D, inv_d, &mean_lo);
   }
+  float s2 = 0.f;
+  #pragma unroll
+  for (int k = 0; k < NV; ++k)
+    if (lane * VEC + k * WAVE * VEC < D) s2 = ln_vec_sqdev(sv[k], mean, s2);
+  const float rstd = ln_rstd(wave_sum(s2), D, eps);
   if (lane == 0) {
     if (!RMS) mean_out[wave_id] = mean;
     rstd_out[wave_id] = rstd;
@@ -332,17 +421,12 @@ add_norm_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b,
   for (int k = 0; k < NV; ++k) {
     const int i = lane * VEC + k * WAVE * VEC;
     if (i < D) {
-      bf16x8 ov, wv, bsv;
+      bf16x8 wv, bsv;
       if (w) wv = *reinterpret_cast<const bf16x8*>(&w[i]);
       if (bias) bsv = *reinterpret_cast<const bf16x8*>(&bias[i]);
-      #pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        float f = (bf2f(sv[k].v[j]) - mean) * rstd;
-        if (w) f *= bf2f(wv.v[j]);
-        if (bias) f += bf2f(bsv.v[j]);
-        ov.v[j] = f2bf(f);
-      }
-      *reinterpret_cast<bf16x8*>(&out[base + i]) = ov;
+      *reinterpret_cast<bf16x8*>(&out[base + i]) =
+          ln_vec_apply(sv[k], wv, bsv, w != nullptr, bias != nullptr, mean,
+                       mean_lo, rstd);
     }
   }
 }

@@ -3,7 +3,8 @@
 The lowering pass (compiler/passes/lower_hip.py) rewrites
 aten.native_layer_norm(_backward) nodes in the sharded graph to these ops,
 so an unmodified user model still runs the gfx950 kernels
-(csrc/norm_kernels.hip: one-pass Welford fwd, two-pass bwd, bf16x8
+(csrc/norm_kernels.hip: fwd takes the mean, then the mean of the squared
+deviations from it, over a row held in registers; two-pass bwd; bf16x8
 vectorized loads — memory-bound ops tuned for the 8 TB/s HBM3E roofline).
 """
 from __future__ import annotations
@@ -196,31 +197,35 @@ def _rms_fwd_cuda(x, w, eps):
     ext = load_extension()
     if ext is not None and x.dtype in (torch.bfloat16, torch.float32) \
             and x.shape[-1] % 8 == 0:
-        return ext.rms_norm_fwd(x.contiguous(),
-                                w.contiguous() if w is not None else None, eps)
+        # the kernel reads w as x's dtype
+        w = w.to(x.dtype).contiguous() if w is not None else None
+        return ext.rms_norm_fwd(x.contiguous(), w, eps)
     return _rms_fwd_aten(x, w, eps)
 
 
 def _rms_bwd_aten(grad, x, rstd, w):
+    """The HIP kernel's contract on aten: fp32 math, dx in x's dtype, dw
+    fp32 [D] = sum over rows of grad * xhat, with or without a weight."""
     xf, gf = x.float(), grad.float()
+    xhat = xf * rstd.float()
+    dw = (gf * xhat).sum(tuple(range(x.dim() - 1)))
     if w is not None:
-        gw = (gf * (xf * rstd)).sum(
-            tuple(range(x.dim() - 1)))
         gf = gf * w.float()
-    else:
-        gw = torch.zeros(x.shape[-1], device=x.device)
-    d = x.shape[-1]
-    xhat = xf * rstd
-    dx = rstd * (gf - xhat * (gf * xhat).mean(-1, keepdim=True))
-    return dx.to(x.dtype), gw.to(w.dtype if w is not None else x.dtype)
+    # the row mean in fp64: an fp32 sum of D terms leaves D * 2^-24 of their
+    # size in dx wherever the mean itself is near 0
+    c2 = (gf * xhat).double().mean(-1, keepdim=True).float()
+    dx = rstd * (gf - xhat * c2)
+    return dx.to(x.dtype), dw
 
 
 def _rms_bwd_cuda(grad, x, rstd, w):
     ext = load_extension()
-    if ext is not None and x.dtype in (torch.bfloat16, torch.float32) \
+    # the backward kernel is bf16 only; fp32 goes to aten
+    if ext is not None and x.dtype == torch.bfloat16 \
             and x.shape[-1] % 8 == 0:
-        return ext.rms_norm_bwd(grad.contiguous(), x.contiguous(), rstd,
-                                w.contiguous() if w is not None else None)
+        w = w.to(x.dtype).contiguous() if w is not None else None
+        return ext.rms_norm_bwd(grad.to(x.dtype).contiguous(), x.contiguous(),
+                                rstd.contiguous(), w)
     return _rms_bwd_aten(grad, x, rstd, w)
 
 
@@ -239,7 +244,22 @@ def _rms_fwd_fake(x, w, eps):
 @torch.library.register_fake("easydist_amd::rms_norm_bwd")
 def _rms_bwd_fake(grad, x, rstd, w):
     d = x.shape[-1]
-    return torch.empty_like(x), x.new_empty((d,))
+    return torch.empty_like(x), x.new_empty((d,), dtype=torch.float32)
+
+
+def _rms_setup(ctx, inputs, output):
+    x, w, _ = inputs
+    ctx.save_for_backward(x, w, output[1])
+
+
+def _rms_backward(ctx, grad_out, grad_rstd):
+    x, w, rstd = ctx.saved_tensors
+    dx, dw = torch.ops.easydist_amd.rms_norm_bwd(grad_out, x, rstd, w)
+    return dx, (dw.to(w.dtype) if w is not None else None), None
+
+
+torch.library.register_autograd("easydist_amd::rms_norm_fwd", _rms_backward,
+                                setup_context=_rms_setup)
 
 
 class RMSNorm(torch.nn.Module):
