@@ -877,6 +877,36 @@ def _register_custom_ops():
             ann[i][1] = ShardDim.get_shard_dim(1)
         return ann, {1: [_gather(1), _gather(1)]}
 
+    # ---- MoE expert FFN forward (ops/moe_ffn.py) ----
+    # Every expert, and every capacity row, is computed on its own, so the
+    # shards run independently: no RUNTIME_REALIZED entry.
+    def _moe_expert_rule(n_w, n_out):
+        # (x [E,R,K], n_w weights [E,K,N][, valid [E,R]]) -> n_out [E,R,N]
+        def rule(input_shapes, args, kwargs):
+            if len(input_shapes[0]) != 3:
+                return None, {}
+            E, R = input_shapes[0][:2]
+            ann = ShardAnnotation.init_from_input_shapes(input_shapes)
+            combs = {}
+            sid = 1
+            if E > 1:     # experts: x, the weights and valid together
+                for i in range(len(input_shapes)):
+                    ann[i][0] = ShardDim.get_shard_dim(sid)
+                combs[sid] = _gather(0) if n_out == 1 \
+                    else [_gather(0)] * n_out
+                sid += 1
+            if R > 1:     # capacity rows: x and valid, weights replicated
+                ann[0][1] = ShardDim.get_shard_dim(sid)
+                if len(input_shapes) > 1 + n_w:
+                    ann[1 + n_w][1] = ShardDim.get_shard_dim(sid)
+                combs[sid] = _gather(1) if n_out == 1 \
+                    else [_gather(1)] * n_out
+            return ann, combs
+        return rule
+
+    register_preset(ed.moe_expert_up.default)(_moe_expert_rule(2, 3))
+    register_preset(ed.moe_expert_gemm.default)(_moe_expert_rule(1, 1))
+
     @register_preset(ed.ce_bwd.default)
     def _ce_bwd_rule(input_shapes, args, kwargs):
         # (grad scalar, logits [N,C], targets [N], lse [N]) -> dlogits

@@ -14,7 +14,11 @@ all-gather+slice reshard fallback, easydist/torch/passes/sharding.py:
   n_experts/ep_world experts: tokens are dispatched
   all_to_all(SHARD(rank)->SHARD(expert)), expert FFNs run batched on the
   local experts, and a second all-to-all returns the results;
-* without a group the same math runs locally (1-GPU path, CPU tests).
+* without a group the same math runs locally (1-GPU path, CPU tests);
+* routing runs on the gfx950 kernels of ops/moe_ops.py; with
+  MoEConfig.grouped_experts the expert FFN forward runs on the grouped
+  NN GEMM kernels of ops/moe_ffn.py (SwiGLU fused, empty capacity tiles
+  skipped) instead of three bmm and an aten silu * mul.  Off by default.
 """
 from __future__ import annotations
 
@@ -46,6 +50,8 @@ class MoEConfig:
     rope_base: float = 10000.0
     # sliding-window causal attention, as GPTConfig.sliding_window
     sliding_window: Optional[int] = None
+    # expert FFN forward on the grouped gfx950 kernels (ExpertFFN.grouped)
+    grouped_experts: bool = False
 
 
 # Mixtral-8x7B shape (per-layer geometry; n_layer reduced variants below)
@@ -70,10 +76,16 @@ def _capacity(tokens: int, n_experts: int, top_k: int,
 class ExpertFFN(nn.Module):
     """SwiGLU expert bank stored as 3 batched weights [E, ...] so the
     per-expert GEMMs run as ONE bmm per projection (MFMA-batched on
-    hipBLASLt) instead of E small launches."""
+    hipBLASLt) instead of E small launches.
 
-    def __init__(self, n_local: int, d: int, h: int):
+    grouped=True runs the forward on the grouped gfx950 kernels instead
+    (ops/moe_ffn.py): one launch for x @ w1, x @ w3 and silu * mul, one for
+    the down projection, both skipping the 128-row tiles that `valid` (the
+    occupancy moe_bins returns) shows empty."""
+
+    def __init__(self, n_local: int, d: int, h: int, grouped: bool = False):
         super().__init__()
+        self.grouped = grouped
         self.w1 = nn.Parameter(torch.empty(n_local, d, h))
         self.w3 = nn.Parameter(torch.empty(n_local, d, h))
         self.w2 = nn.Parameter(torch.empty(n_local, h, d))
@@ -81,10 +93,22 @@ class ExpertFFN(nn.Module):
             nn.init.normal_(w, std=0.02)
         nn.init.normal_(self.w2, std=0.02 / math.sqrt(2.0))
 
-    def forward(self, x):           # x: [E_local, capacity*, d]
+    def forward(self, x, valid=None):   # x: [E_local, capacity*, d]
+        if self.grouped:
+            return self._forward_grouped(x, valid)
         a = torch.bmm(x, self.w1)
         b = torch.bmm(x, self.w3)
         return torch.bmm(F.silu(a) * b, self.w2)
+
+    def _forward_grouped(self, x, valid):
+        from ..ops import moe_ffn
+        w1, w3, w2 = self.w1, self.w3, self.w2
+        if torch.is_autocast_enabled(x.device.type):
+            # custom ops do not autocast; bmm would make the same casts
+            dt = torch.get_autocast_dtype(x.device.type)
+            x, w1, w3, w2 = (t.to(dt) for t in (x, w1, w3, w2))
+        h, _, _ = moe_ffn.moe_expert_up(x, w1, w3, valid)
+        return moe_ffn.moe_expert_gemm(h, w2, valid)
 
 
 class MoELayer(nn.Module):
@@ -103,7 +127,8 @@ class MoELayer(nn.Module):
         assert cfg.n_experts % self.ep_world == 0
         self.n_local = cfg.n_experts // self.ep_world
         self.router = nn.Linear(cfg.n_embd, cfg.n_experts, bias=False)
-        self.experts = ExpertFFN(self.n_local, cfg.n_embd, cfg.ffn_hidden)
+        self.experts = ExpertFFN(self.n_local, cfg.n_embd, cfg.ffn_hidden,
+                                 grouped=cfg.grouped_experts)
 
     def forward(self, x):
         B, T, C = x.shape
@@ -134,13 +159,15 @@ class MoELayer(nn.Module):
             recv = comm.all_to_all_ep(bins, self.ep_group)
             expert_in = recv.reshape(W, L, cap, C).transpose(0, 1) \
                 .reshape(L, W * cap, C)
+            # expert_in is W capacity slices side by side; `valid` is not
+            # exchanged with them yet, so nothing is skipped on this path
             expert_out = self.experts(expert_in)
             send_back = expert_out.reshape(L, W, cap, C).transpose(0, 1) \
                 .reshape(W * L, cap, C).contiguous()
             out_bins = comm.all_to_all_ep(send_back, self.ep_group)
             out_bins = out_bins.reshape(E, cap, C)
         else:
-            out_bins = self.experts(bins).reshape(E, cap, C)
+            out_bins = self.experts(bins, valid).reshape(E, cap, C)
 
         # combine: weighted scatter-add back to token positions
         out = torch.ops.easydist_amd.moe_combine(

@@ -90,6 +90,11 @@ std::tuple<at::Tensor, at::Tensor>
 moe_combine_bwd(const at::Tensor& gout, const at::Tensor& bins,
                 const at::Tensor& gates, const at::Tensor& src,
                 const at::Tensor& valid, int64_t top_k);
+std::tuple<at::Tensor, at::Tensor, at::Tensor>
+moe_expert_up(const at::Tensor& x, const at::Tensor& w1, const at::Tensor& w3,
+              const std::optional<at::Tensor>& valid);
+at::Tensor moe_expert_gemm(const at::Tensor& x, const at::Tensor& w,
+                           const std::optional<at::Tensor>& valid);
 
 // wrappers adapting std::vector<bool> / TensorList signatures
 static std::tuple<at::Tensor, at::Tensor, at::Tensor>
@@ -183,6 +188,9 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
         "Tensor valid, int n_tokens, int top_k) -> Tensor");
   m.def("moe_combine_bwd(Tensor gout, Tensor bins, Tensor gates, Tensor src, "
         "Tensor valid, int top_k) -> (Tensor, Tensor)");
+  m.def("moe_expert_up(Tensor x, Tensor w1, Tensor w3, Tensor? valid) "
+        "-> (Tensor, Tensor, Tensor)");
+  m.def("moe_expert_gemm(Tensor x, Tensor w, Tensor? valid) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
@@ -214,6 +222,8 @@ TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
   m.impl("moe_bins_bwd", moe_bins_bwd);
   m.impl("moe_combine_fwd", moe_combine_fwd);
   m.impl("moe_combine_bwd", moe_combine_bwd);
+  m.impl("moe_expert_up", moe_expert_up);
+  m.impl("moe_expert_gemm", moe_expert_gemm);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {}

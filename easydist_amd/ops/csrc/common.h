@@ -31,6 +31,12 @@ DEVINL float wave_max(float x) {
   return __shfl(x, 0, WAVE);
 }
 
+// the sigmoid of the SwiGLU kernels (swiglu_kernels.hip, and the fused
+// epilogue of the MoE expert GEMM): one v_exp and one v_rcp.  exp(-g)
+// overflowing gives 1/inf = 0, never NaN.
+DEVINL float swiglu_sigmoid(float g) {
+  return __builtin_amdgcn_rcpf(1.f + __expf(-g));
+}
 
 // wait for LDS (lgkm) traffic only — unlike s_waitcnt(0) this does NOT
 // flush vmcnt, so in-flight global prefetch loads keep overlapping.

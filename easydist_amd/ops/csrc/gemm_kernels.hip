@@ -1,7 +1,9 @@
 // Hand-written MFMA bf16 GEMM family for gfx950.
 //
 // Three kernel families cover the linear-layer training shapes the
-// compiler's lowering pass (compiler/passes/lower_hip.py) emits:
+// compiler's lowering pass (compiler/passes/lower_hip.py) emits, and a
+// fourth, moe_nn (grouped NN, optional fused SwiGLU; described at its
+// definition), the MoE expert FFN forward:
 //
 //   gemm_nt_256  C[M,N] = A[M,K] @ Bt[N,K]^T (+bias)  -- fwd linears and,
 //       with a (cheap, weight-only) transpose in the graph, the dX
@@ -722,6 +724,241 @@ TN_KERNEL(gemm_tn_kernel, TBP, 0)
 TN_KERNEL(gemm_tn_256_kernel, TBP2, 1)
 TN_KERNEL(gemm_tn_256_drain_kernel, TBP2, 0)
 
+// ===========================================================================
+// moe_nn: the MoE expert FFN forward, one grouped NN GEMM template.
+//   plain :  C[e] = X[e] @ W[e]           X [E,R,K], W [E,K,N] -> C [E,R,N]
+//   swiglu:  A[e] = X[e] @ W1[e], B[e] = X[e] @ W3[e],
+//            H[e] = silu(A[e]) * B[e]     -> H, A, B [E,R,N]
+// Expert weights are [K,N] with the reduce dim strided, so neither NT
+// kernel serves them without a weight-sized transpose per call.  This kernel
+// joins the two stagings the file already has: X rows are K-contiguous and
+// stage like gemm_nt_128's A tile (128 rows x 32 k, source rows clamped to
+// R-1); W rows ARE k-rows and stage k-major through tn_stage into the
+// tr-read image, whose tn_frag gives the MFMA operand "n = l&15,
+// k = 8*(l>>4)+0..7" that the linear X tile gives for its rows.
+//
+// One workgroup (4 waves) owns (expert, 128-row tile, column tile):
+//   plain   128 columns, waves of 64x64, acc[4][4]
+//   swiglu   64 columns of W1 and the same 64 of W3 (waves 0-1 stage the W1
+//            image, waves 2-3 the W3 image), waves of 64x32 against both:
+//            two acc[4][2] sets, the X tile staged ONCE for both products.
+// Both keep 32 KiB of LDS, double-buffered: stage k+1, compute k, wait,
+// barrier (the gemm_nt_128 / tn_body<128,0> loop).
+//
+// The MFMAs run transposed (W fragment as the A operand), so a lane ends
+// with 4 CONSECUTIVE columns of one output row: 8-byte LDS writes into an
+// XOR-swizzled [128][columns] bf16 tile (16-byte chunk c of row r sits at
+// c ^ (r & (chunks-1))), read back as 16-byte vectors and stored as whole
+// rows.  N % 8 == 0, so a vector is inside or outside the edge, never
+// across it.  H comes from the fp32 accumulators and is rounded once.
+//
+// valid [E,R] (optional): a workgroup whose (at most 128) row flags are all
+// clear writes zeros to its tile(s) and returns without touching X or W.
+// Rows of X with a clear flag are zero by contract (moe_bins writes them),
+// so skipping changes no output bit.  The zeros are plain stores: no
+// memset node enters a captured graph (moe_kernels.hip's header).
+//
+// Block ids run row tile fastest, then column tile, then expert:
+// consecutive workgroups share one [K, columns] weight panel.
+// ===========================================================================
+#define NN_BM 128
+#define NN_BK 32
+using bf16x4v = __attribute__((ext_vector_type(4))) __bf16;
+
+template <bool SWIGLU>
+DEVINL void moe_nn_body(const bf16* __restrict__ X,
+                        const bf16* __restrict__ W1,
+                        const bf16* __restrict__ W3, bf16* __restrict__ Out,
+                        bf16* __restrict__ Aout, bf16* __restrict__ Bout,
+                        const unsigned char* __restrict__ valid, int R, int K,
+                        int N) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NP = SWIGLU ? 2 : 1;           // products per workgroup
+  constexpr int TN = SWIGLU ? 64 : 128;        // output columns per product
+  constexpr int NJ = TN / 32;                  // 16-col fragments per wave
+  constexpr int CV = TN / 8;                   // 16-byte chunks per tile row
+  constexpr unsigned ATILE = NN_BM * NN_BK * 2;   // X tile, 8 KiB
+  constexpr unsigned WIMG = NN_BK * TN * 2;       // one W image, 8 / 4 KiB
+  constexpr unsigned BUF = ATILE + NP * WIMG;     // 16 KiB per buffer
+  constexpr unsigned OTILE = NN_BM * TN * 2;      // epilogue tile, 32 / 16 KiB
+
+  const unsigned nrt = (R + NN_BM - 1) / NN_BM, nct = (N + TN - 1) / TN;
+  const int m0 = (blockIdx.x % nrt) * NN_BM;
+  const int n0 = ((blockIdx.x / nrt) % nct) * TN;
+  const long e = blockIdx.x / (nrt * nct);
+  const long row0 = e * R;                     // expert e's first row
+
+  const int t = threadIdx.x;
+  const int lane = t % WAVE;
+  const int wave = t / WAVE;
+  const int wm = (wave / 2) * 64;              // wave row offset in the tile
+  const int wn = (wave % 2) * (TN / 2);        // wave column offset
+
+  // one output tile as whole rows of 16-byte vectors, vec(row, chunk) each
+  auto store_tile = [&](bf16* __restrict__ dst, auto vec) {
+    #pragma unroll
+    for (int it = 0; it < NN_BM * CV / 256; ++it) {
+      const int idx = it * 256 + t;
+      const int row = idx / CV, c = idx % CV;
+      const int gm = m0 + row, gn = n0 + c * 8;
+      if (gm < R && gn < N)
+        *reinterpret_cast<bf16x8v*>(dst + (row0 + gm) * N + gn) = vec(row, c);
+    }
+  };
+  auto zeros = [](int, int) { return bf16x8v{}; };
+  // ... from the swizzled epilogue tile in LDS
+  auto from = [](const char* tile) {
+    return [tile](int row, int c) {
+      return *reinterpret_cast<const bf16x8v*>(
+          tile + row * (TN * 2) + ((c ^ (row & (CV - 1))) * 16));
+    };
+  };
+
+  if (valid) {
+    // every wave reads all 128 flags, two per lane, and ballots: the same
+    // answer in all four waves with no LDS object beside smem (a second one
+    // makes hipcc drain vmcnt before every ds_read, see gemm_nt_256)
+    const int r = m0 + lane;
+    const int any = (r < R ? (int)valid[row0 + r] : 0)
+                  | (r + 64 < R ? (int)valid[row0 + r + 64] : 0);
+    if (__ballot(any) == 0) {
+      store_tile(Out, zeros);
+      if constexpr (SWIGLU) {
+        store_tile(Aout, zeros);
+        store_tile(Bout, zeros);
+      }
+      return;
+    }
+  }
+
+  const bf16* Xe = X + row0 * K;
+  const bf16* W1e = W1 + e * K * N;
+  const bf16* W3e = SWIGLU ? W3 + e * K * N : nullptr;
+
+  auto stage = [&](int buf, int k0) {
+    char* dst = smem + buf * BUF;
+    #pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int el = (t + p * 256) * 8;        // element offset in the tile
+      const int row = el / NN_BK, col = el % NN_BK;
+      const int grow = min(m0 + row, R - 1);
+      glds16(Xe + (long)grow * K + k0 + col,
+             dst + (p * 256 + wave * 64) * 16);
+    }
+    if constexpr (SWIGLU)
+      tn_stage<128>(wave < 2 ? W1e : W3e, N, k0, n0, N,
+                    dst + ATILE + (wave >> 1) * WIMG, t & 127, wave & 1);
+    else
+      tn_stage<256>(W1e, N, k0, n0, N, dst + ATILE, t, wave);
+  };
+
+  f32x4 acc[NP][4][NJ];
+  #pragma unroll
+  for (int p = 0; p < NP; ++p)
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        acc[p][i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  stage(0, 0);
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+
+  const int frag_row = lane & 15;
+  const int frag_k = (lane >> 4) * 8;
+  const int nk = K / NN_BK;
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nk) stage(buf ^ 1, (kt + 1) * NN_BK);
+    const char* base = smem + buf * BUF;
+    bf16x8v x_frag[4], w_frag[NP][NJ];
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      x_frag[i] = *reinterpret_cast<const bf16x8v*>(
+          base + ((wm + i * 16 + frag_row) * NN_BK + frag_k) * 2);
+    #pragma unroll
+    for (int p = 0; p < NP; ++p)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        w_frag[p][j] = tn_frag(base + ATILE + p * WIMG, (wn >> 4) + j, lane);
+    // transposed product: D[n][row], a lane holds row (l&15) and columns
+    // (l>>4)*4 + 0..3 of each 16x16 block
+    #pragma unroll
+    for (int p = 0; p < NP; ++p)
+      #pragma unroll
+      for (int i = 0; i < 4; ++i)
+        #pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          acc[p][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              w_frag[p][j], x_frag[i], acc[p][i][j], 0, 0, 0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+  }
+
+  // 4 columns of one row, rounded, into the swizzled epilogue tile
+  auto put = [&](char* tile, int i, int j, f32x4 v) {
+    const int row = wm + i * 16 + (lane & 15);
+    const int col = wn + j * 16 + (lane >> 4) * 4;
+    bf16x4v o;
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = (__bf16)v[r];
+    *reinterpret_cast<bf16x4v*>(
+        tile + row * (TN * 2) + (((col >> 3) ^ (row & (CV - 1))) * 16)
+        + (col & 4) * 2) = o;
+  };
+
+  if constexpr (SWIGLU) {
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const f32x4 a = acc[0][i][j], b = acc[1][i][j];
+        f32x4 h;
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) h[r] = a[r] * swiglu_sigmoid(a[r]) * b[r];
+        put(smem, i, j, h);
+        put(smem + OTILE, i, j, a);
+      }
+    __syncthreads();
+    store_tile(Out, from(smem));
+    store_tile(Aout, from(smem + OTILE));
+    __syncthreads();
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        put(smem, i, j, acc[1][i][j]);
+    __syncthreads();
+    store_tile(Bout, from(smem));
+  } else {
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        put(smem, i, j, acc[0][i][j]);
+    __syncthreads();
+    store_tile(Out, from(smem));
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+moe_nn_gemm_kernel(const bf16* __restrict__ X, const bf16* __restrict__ W,
+                   bf16* __restrict__ C,
+                   const unsigned char* __restrict__ valid, int R, int K,
+                   int N) {
+  moe_nn_body<false>(X, W, nullptr, C, nullptr, nullptr, valid, R, K, N);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+moe_nn_swiglu_kernel(const bf16* __restrict__ X, const bf16* __restrict__ W1,
+                     const bf16* __restrict__ W3, bf16* __restrict__ H,
+                     bf16* __restrict__ A, bf16* __restrict__ B,
+                     const unsigned char* __restrict__ valid, int R, int K,
+                     int N) {
+  moe_nn_body<true>(X, W1, W3, H, A, B, valid, R, K, N);
+}
+
 
 // ===========================================================================
 // host wrappers
@@ -911,4 +1148,73 @@ std::tuple<at::Tensor, at::Tensor> gemm_tn_asum(const at::Tensor& a,
   auto asum = at::zeros({a.size(1)}, a.options().dtype(at::kFloat));
   auto cw = tn_launch(a, b, asum.data_ptr<float>());
   return {cw.to(at::kBFloat16), asum};
+}
+
+// ---------------------------------------------------------------------------
+// MoE expert FFN forward (moe_nn kernels)
+// ---------------------------------------------------------------------------
+struct MoeNnShape { long E, R, K, N; unsigned grid; };
+
+static void moe_nn_operand(const at::Tensor& t, at::IntArrayRef shape,
+                           const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dtype() == at::kBFloat16 && t.is_contiguous(),
+              "moe_expert: ", name, " must be a contiguous bf16 device tensor");
+  TORCH_CHECK(t.sizes() == shape, "moe_expert: ", name, " has the wrong shape");
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, "moe_expert: ", name,
+              " must be 16-byte aligned");
+}
+
+static MoeNnShape moe_nn_shape(const at::Tensor& x, const at::Tensor& w,
+                               const std::optional<at::Tensor>& valid,
+                               int tile_n) {
+  TORCH_CHECK(x.dim() == 3 && w.dim() == 3, "moe_expert: x [E,R,K], w [E,K,N]");
+  MoeNnShape s{x.size(0), x.size(1), x.size(2), w.size(2), 0};
+  TORCH_CHECK(s.E >= 1 && s.R >= 1 && s.K >= NN_BK && s.K % NN_BK == 0 &&
+              s.N >= 8 && s.N % 8 == 0,
+              "moe_expert: E, R >= 1, K % 32 == 0, N % 8 == 0");
+  TORCH_CHECK(s.R < (1L << 31) && s.K < (1L << 31) && s.N < (1L << 31));
+  moe_nn_operand(x, {s.E, s.R, s.K}, "x");
+  moe_nn_operand(w, {s.E, s.K, s.N}, "w");
+  if (valid)
+    TORCH_CHECK(valid->is_cuda() && valid->dtype() == at::kBool &&
+                valid->is_contiguous() && valid->dim() == 2 &&
+                valid->size(0) == s.E && valid->size(1) == s.R,
+                "moe_expert: valid must be a contiguous bool [E,R]");
+  const long nwg = s.E * ((s.R + NN_BM - 1) / NN_BM)
+                   * ((s.N + tile_n - 1) / tile_n);
+  TORCH_CHECK(nwg < (1L << 31), "moe_expert: too many tiles for one launch");
+  s.grid = (unsigned)nwg;
+  return s;
+}
+
+static const unsigned char* moe_nn_valid(const std::optional<at::Tensor>& v) {
+  return v ? (const unsigned char*)v->data_ptr() : nullptr;
+}
+
+at::Tensor moe_expert_gemm(const at::Tensor& x, const at::Tensor& w,
+                           const std::optional<at::Tensor>& valid) {
+  const MoeNnShape s = moe_nn_shape(x, w, valid, 128);
+  auto c = at::empty({s.E, s.R, s.N}, x.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(moe_nn_gemm_kernel, dim3(s.grid), dim3(256), 32768,
+      stream, (const bf16*)x.data_ptr(), (const bf16*)w.data_ptr(),
+      (bf16*)c.data_ptr(), moe_nn_valid(valid), (int)s.R, (int)s.K, (int)s.N);
+  return c;
+}
+
+// (h, a, b) = (silu(a) * b, x @ w1, x @ w3)
+std::tuple<at::Tensor, at::Tensor, at::Tensor>
+moe_expert_up(const at::Tensor& x, const at::Tensor& w1, const at::Tensor& w3,
+              const std::optional<at::Tensor>& valid) {
+  const MoeNnShape s = moe_nn_shape(x, w1, valid, 64);
+  moe_nn_operand(w3, {s.E, s.K, s.N}, "w3");
+  auto h = at::empty({s.E, s.R, s.N}, x.options());
+  auto a = at::empty_like(h);
+  auto b = at::empty_like(h);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(moe_nn_swiglu_kernel, dim3(s.grid), dim3(256), 32768,
+      stream, (const bf16*)x.data_ptr(), (const bf16*)w1.data_ptr(),
+      (const bf16*)w3.data_ptr(), (bf16*)h.data_ptr(), (bf16*)a.data_ptr(),
+      (bf16*)b.data_ptr(), moe_nn_valid(valid), (int)s.R, (int)s.K, (int)s.N);
+  return {h, a, b};
 }

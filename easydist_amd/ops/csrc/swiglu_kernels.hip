@@ -27,10 +27,6 @@ struct SwigluShape {
   long stride_g, stride_u, stride_dy;   // row strides in elements
 };
 
-DEVINL float swiglu_sigmoid(float g) {
-  return __builtin_amdgcn_rcpf(1.f + __expf(-g));
-}
-
 __global__ void __launch_bounds__(SWIGLU_BLOCK)
 swiglu_fwd_kernel(const bf16* __restrict__ G, const bf16* __restrict__ U,
                   bf16* __restrict__ Y, SwigluShape p) {
