@@ -907,6 +907,55 @@ def _register_custom_ops():
     register_preset(ed.moe_expert_up.default)(_moe_expert_rule(2, 3))
     register_preset(ed.moe_expert_gemm.default)(_moe_expert_rule(1, 1))
 
+    # ---- MoE expert FFN backward (ops/moe_ffn.py) ----
+    # input_shapes holds the tensor arguments only: valid is the 2-D one,
+    # and for dx the 3-D ones alternate g [E,R,N], w [E,K,N].
+    @register_preset(ed.moe_expert_dx.default)
+    def _moe_expert_dx_rule(input_shapes, args, kwargs):
+        if len(input_shapes[0]) != 3:
+            return None, {}
+        E, R = input_shapes[0][:2]
+        ann = ShardAnnotation.init_from_input_shapes(input_shapes)
+        combs = {}
+        sid = 1
+        if E > 1:         # experts: every operand
+            for i in range(len(input_shapes)):
+                ann[i][0] = ShardDim.get_shard_dim(sid)
+            combs[sid] = _gather(0)
+            sid += 1
+        if R > 1:         # capacity rows: g and valid, weights replicated
+            for i, shape in enumerate(input_shapes):
+                if len(shape) == 2 or i % 2 == 0:
+                    ann[i][1] = ShardDim.get_shard_dim(sid)
+            combs[sid] = _gather(1)
+        return ann, combs
+
+    def _moe_expert_dw_rule(n_out):
+        # (x [E,R,K], n_out g [E,R,N][, valid [E,R]]) -> n_out [E,K,N]
+        def rule(input_shapes, args, kwargs):
+            if len(input_shapes[0]) != 3:
+                return None, {}
+            E, R = input_shapes[0][:2]
+            ann = ShardAnnotation.init_from_input_shapes(input_shapes)
+            combs = {}
+            sid = 1
+            if E > 1:
+                for i in range(len(input_shapes)):
+                    ann[i][0] = ShardDim.get_shard_dim(sid)
+                combs[sid] = _gather(0) if n_out == 1 \
+                    else [_gather(0)] * n_out
+                sid += 1
+            if R > 1:     # the reduce dim: every operand, a sum-partial
+                for i in range(len(input_shapes)):
+                    ann[i][1] = ShardDim.get_shard_dim(sid)
+                combs[sid] = _reduce_add() if n_out == 1 \
+                    else [_reduce_add()] * n_out
+            return ann, combs
+        return rule
+
+    register_preset(ed.moe_expert_dw.default)(_moe_expert_dw_rule(1))
+    register_preset(ed.moe_expert_dw2.default)(_moe_expert_dw_rule(2))
+
     @register_preset(ed.ce_bwd.default)
     def _ce_bwd_rule(input_shapes, args, kwargs):
         # (grad scalar, logits [N,C], targets [N], lse [N]) -> dlogits

@@ -81,7 +81,8 @@ class ExpertFFN(nn.Module):
     grouped=True runs the forward on the grouped gfx950 kernels instead
     (ops/moe_ffn.py): one launch for x @ w1, x @ w3 and silu * mul, one for
     the down projection, both skipping the 128-row tiles that `valid` (the
-    occupancy moe_bins returns) shows empty."""
+    occupancy moe_bins returns) shows empty; their autograd runs the
+    grouped dX and dW kernels with the same `valid`."""
 
     def __init__(self, n_local: int, d: int, h: int, grouped: bool = False):
         super().__init__()

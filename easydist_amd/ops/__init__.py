@@ -3,7 +3,7 @@
 The compute path of the framework (SURVEY.md §7 phase 5): partitioned hot
 ops in the lowered graph run as gfx950 kernels — MFMA-tiled GEMM, flash
 attention, rotary embeddings, fused SwiGLU, MoE routing, the MoE expert FFN
-forward (grouped GEMM with fused SwiGLU), LayerNorm fwd/bwd, fused
+(grouped GEMMs: forward with fused SwiGLU, dX and dW), LayerNorm fwd/bwd, fused
 multi-tensor Adam, fused cross-entropy.
 Plain large GEMMs go to hipBLASLt via aten (torch.mm); everything listed
 here is a hand kernel.

@@ -95,6 +95,15 @@ moe_expert_up(const at::Tensor& x, const at::Tensor& w1, const at::Tensor& w3,
               const std::optional<at::Tensor>& valid);
 at::Tensor moe_expert_gemm(const at::Tensor& x, const at::Tensor& w,
                            const std::optional<at::Tensor>& valid);
+at::Tensor moe_expert_dx(const at::Tensor& g1, const at::Tensor& w1,
+                         const std::optional<at::Tensor>& g2,
+                         const std::optional<at::Tensor>& w2,
+                         const std::optional<at::Tensor>& valid);
+at::Tensor moe_expert_dw(const at::Tensor& x, const at::Tensor& g,
+                         const std::optional<at::Tensor>& valid);
+std::tuple<at::Tensor, at::Tensor>
+moe_expert_dw2(const at::Tensor& x, const at::Tensor& g1, const at::Tensor& g2,
+               const std::optional<at::Tensor>& valid);
 
 // wrappers adapting std::vector<bool> / TensorList signatures
 static std::tuple<at::Tensor, at::Tensor, at::Tensor>
@@ -191,6 +200,11 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
   m.def("moe_expert_up(Tensor x, Tensor w1, Tensor w3, Tensor? valid) "
         "-> (Tensor, Tensor, Tensor)");
   m.def("moe_expert_gemm(Tensor x, Tensor w, Tensor? valid) -> Tensor");
+  m.def("moe_expert_dx(Tensor g1, Tensor w1, Tensor? g2, Tensor? w2, "
+        "Tensor? valid) -> Tensor");
+  m.def("moe_expert_dw(Tensor x, Tensor g, Tensor? valid) -> Tensor");
+  m.def("moe_expert_dw2(Tensor x, Tensor g1, Tensor g2, Tensor? valid) "
+        "-> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
@@ -224,6 +238,9 @@ TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
   m.impl("moe_combine_bwd", moe_combine_bwd);
   m.impl("moe_expert_up", moe_expert_up);
   m.impl("moe_expert_gemm", moe_expert_gemm);
+  m.impl("moe_expert_dx", moe_expert_dx);
+  m.impl("moe_expert_dw", moe_expert_dw);
+  m.impl("moe_expert_dw2", moe_expert_dw2);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {}

@@ -959,6 +959,367 @@ moe_nn_swiglu_kernel(const bf16* __restrict__ X, const bf16* __restrict__ W1,
   moe_nn_body<true>(X, W1, W3, H, A, B, valid, R, K, N);
 }
 
+// ===========================================================================
+// moe_nt / moe_tn: the MoE expert FFN backward, grouped like moe_nn.
+//   moe_nt (dX):  DX[e] = G1[e] @ W1[e]^T (+ G2[e] @ W2[e]^T)
+//                 G [E,R,N], W [E,K,N] -> DX [E,R,K]
+//   moe_tn (dW):  DW[e] = X[e]^T @ G[e]       X [E,R,K], G [E,R,N] -> [E,K,N]
+//                 pair: DW1 = X^T @ G1 and DW3 = X^T @ G2 from one X image
+// Both write bf16 from fp32 accumulators, each output rounded once, through
+// moe_nn's XOR-swizzled epilogue tile (the MFMAs run transposed, so a lane
+// ends with 4 consecutive columns of one output row) to whole-row 16-byte
+// stores.  No atomics, no workspace: one workgroup owns one output tile.
+//
+// moe_nt: both operands are contiguous along the reduce dim N and stage like
+// gemm_nt_128's tiles (128 rows x 32 n, source rows clamped to the operand's
+// last row); 32 KiB double-buffered.  The two-product form runs ONE k-loop of
+// 2 N/32 steps, the first half reading (G1, W1), the second (G2, W2), into the
+// same accumulators: da @ w1^T + db @ w3^T leaves fp32 once.  A tile none of
+// whose rows is valid is written as zeros (moe_nn's ballot test).  Block ids
+// run row tile fastest, then column tile, then expert.
+//
+// moe_tn: both operands are R-strided and stage k(r)-major through tn_stage
+// into tr-read images, as tn_body does.  One workgroup per (expert, 128 x 128
+// output tile); the pair form stages the 128-wide X image ONCE per r-step
+// against 64 columns of G1 and the same 64 of G2 (waves 0-1 stage G1, waves
+// 2-3 G2), two acc[4][2] sets -- the mirror image of moe_nn's SwiGLU form.
+// R need not be a multiple of 32: the partial last step goes through
+// predicated register loads with zero fill (tn_stage_tail), so rows at or
+// beyond R contribute nothing and nothing past the expert is read.
+// With valid, every wave reads the expert's R flags (16-byte loads where the
+// address allows), ballots per 32-row step and writes the same compact list
+// of live steps, one uint16 each, behind the staging buffers in the dynamic
+// LDS region (ceil(R/32) <= 4096: at most 8 KiB); the r-loop walks that list.
+// Rows of X and G with a clear flag are zero by contract, so a skipped step
+// changes no output bit; with no live step the tile is written as zeros.
+// Block ids run K tile fastest, then N tile, then expert.
+// ===========================================================================
+// 4 columns (col % 4 == 0) of one row, rounded, into a swizzled [128][TN] tile
+template <int TN>
+DEVINL void moe_tile_put(char* tile, int row, int col, f32x4 v) {
+  bf16x4v o;
+  #pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = (__bf16)v[r];
+  *reinterpret_cast<bf16x4v*>(
+      tile + row * (TN * 2) + (((col >> 3) ^ (row & (TN / 8 - 1))) * 16)
+      + (col & 4) * 2) = o;
+}
+
+// a [128][TN] tile as whole rows of 16-byte vectors to dst[rows][ld] at
+// (m0, n0); from the swizzled LDS tile, or zeros when tile is null
+template <int TN>
+DEVINL void moe_tile_store(bf16* __restrict__ dst, long ld, int m0, int n0,
+                           int rows, const char* tile, int t) {
+  constexpr int CV = TN / 8;
+  #pragma unroll
+  for (int it = 0; it < NN_BM * CV / 256; ++it) {
+    const int idx = it * 256 + t;
+    const int row = idx / CV, c = idx % CV;
+    const int gm = m0 + row, gn = n0 + c * 8;
+    if (gm < rows && gn < ld)
+      *reinterpret_cast<bf16x8v*>(dst + (long)gm * ld + gn) = tile
+          ? *reinterpret_cast<const bf16x8v*>(
+                tile + row * (TN * 2) + ((c ^ (row & (CV - 1))) * 16))
+          : bf16x8v{};
+  }
+}
+
+template <bool TWO>
+DEVINL void moe_nt_body(const bf16* __restrict__ G1,
+                        const bf16* __restrict__ W1,
+                        const bf16* __restrict__ G2,
+                        const bf16* __restrict__ W2, bf16* __restrict__ DX,
+                        const unsigned char* __restrict__ valid, int R, int K,
+                        int N) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr unsigned ATILE = NN_BM * NN_BK * 2;   // one operand tile, 8 KiB
+  constexpr unsigned BUF = 2 * ATILE;             // G + W per buffer
+
+  const unsigned nrt = (R + NN_BM - 1) / NN_BM, nct = (K + 127) / 128;
+  const int m0 = (blockIdx.x % nrt) * NN_BM;      // first row of the tile
+  const int c0 = ((blockIdx.x / nrt) % nct) * 128;   // first column (k index)
+  const long e = blockIdx.x / (nrt * nct);
+  const long row0 = e * R;
+
+  const int t = threadIdx.x;
+  const int lane = t % WAVE;
+  const int wave = t / WAVE;
+  const int wm = (wave / 2) * 64;
+  const int wn = (wave % 2) * 64;
+  bf16* DXe = DX + row0 * K;
+
+  if (valid) {
+    const int r = m0 + lane;
+    const int any = (r < R ? (int)valid[row0 + r] : 0)
+                  | (r + 64 < R ? (int)valid[row0 + r + 64] : 0);
+    if (__ballot(any) == 0) {
+      moe_tile_store<128>(DXe, K, m0, c0, R, nullptr, t);
+      return;
+    }
+  }
+
+  const int nk = N / NN_BK;
+  const int nsteps = TWO ? 2 * nk : nk;
+  auto stage = [&](int buf, int kt) {
+    const bool second = TWO && kt >= nk;
+    const bf16* Ge = (second ? G2 : G1) + row0 * N;
+    const bf16* We = (second ? W2 : W1) + e * K * N;
+    const int k0 = (second ? kt - nk : kt) * NN_BK;
+    char* dst = smem + buf * BUF;
+    #pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int el = (t + p * 256) * 8;        // element offset in the tile
+      const int row = el / NN_BK, col = el % NN_BK;
+      glds16(Ge + (long)min(m0 + row, R - 1) * N + k0 + col,
+             dst + (p * 256 + wave * 64) * 16);
+      glds16(We + (long)min(c0 + row, K - 1) * N + k0 + col,
+             dst + ATILE + (p * 256 + wave * 64) * 16);
+    }
+  };
+
+  f32x4 acc[4][4];
+  #pragma unroll
+  for (int i = 0; i < 4; ++i)
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  stage(0, 0);
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+
+  const int frag_row = lane & 15;
+  const int frag_k = (lane >> 4) * 8;
+  for (int kt = 0; kt < nsteps; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nsteps) stage(buf ^ 1, kt + 1);
+    const char* base = smem + buf * BUF;
+    bf16x8v g_frag[4], w_frag[4];
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      g_frag[i] = *reinterpret_cast<const bf16x8v*>(
+          base + ((wm + i * 16 + frag_row) * NN_BK + frag_k) * 2);
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      w_frag[j] = *reinterpret_cast<const bf16x8v*>(
+          base + ATILE + ((wn + j * 16 + frag_row) * NN_BK + frag_k) * 2);
+    // transposed product D[k][row]: a lane holds row (l&15) and columns
+    // (l>>4)*4 + 0..3 of each 16x16 block
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            w_frag[j], g_frag[i], acc[i][j], 0, 0, 0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+  }
+
+  #pragma unroll
+  for (int i = 0; i < 4; ++i)
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      moe_tile_put<128>(smem, wm + i * 16 + (lane & 15),
+                        wn + j * 16 + (lane >> 4) * 4, acc[i][j]);
+  __syncthreads();
+  moe_tile_store<128>(DXe, K, m0, c0, R, smem, t);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+moe_nt_kernel(const bf16* __restrict__ G, const bf16* __restrict__ W,
+              bf16* __restrict__ DX, const unsigned char* __restrict__ valid,
+              int R, int K, int N) {
+  moe_nt_body<false>(G, W, nullptr, nullptr, DX, valid, R, K, N);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+moe_nt2_kernel(const bf16* __restrict__ G1, const bf16* __restrict__ W1,
+               const bf16* __restrict__ G2, const bf16* __restrict__ W2,
+               bf16* __restrict__ DX, const unsigned char* __restrict__ valid,
+               int R, int K, int N) {
+  moe_nt_body<true>(G1, W1, G2, W2, DX, valid, R, K, N);
+}
+
+// tn_stage's image for a step that crosses the operand's last row: the same
+// positions, through registers, rows at or beyond rmax filled with zeros
+template <int NTHR>
+DEVINL void tn_stage_tail(const bf16* src, long ld, int r0, int rmax, int p0,
+                          int pmax, char* dst_base, int t) {
+  #pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    unsigned p = (i * NTHR + t) * 16;
+    int chunk16 = p >> 10;
+    unsigned w = p & 1023u;
+    int rr = tn_unswz(w >> 7) * 4 + ((w & 127) >> 5);
+    int pp = chunk16 * 16 + ((w & 31) >> 1);
+    int gp = min(p0 + pp, pmax - 8);
+    bf16x8v v{};
+    if (r0 + rr < rmax)
+      v = *reinterpret_cast<const bf16x8v*>(src + (long)(r0 + rr) * ld + gp);
+    *reinterpret_cast<bf16x8v*>(dst_base + p) = v;
+  }
+}
+
+#define MOE_TN_LIST 32768u     // the live-step list sits behind the buffers
+
+template <bool PAIR>
+DEVINL void moe_tn_body(const bf16* __restrict__ X, const bf16* __restrict__ G1,
+                        const bf16* __restrict__ G2, bf16* __restrict__ DW1,
+                        bf16* __restrict__ DW3,
+                        const unsigned char* __restrict__ valid, int R, int K,
+                        int N) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NP = PAIR ? 2 : 1;             // products per workgroup
+  constexpr int TN = PAIR ? 64 : 128;          // output columns per product
+  constexpr int NJ = TN / 32;                  // 16-col fragments per wave
+  constexpr unsigned XIMG = TBR * 128 * 2;     // X image, 8 KiB
+  constexpr unsigned GIMG = TBR * TN * 2;      // one G image, 8 / 4 KiB
+  constexpr unsigned BUF = XIMG + NP * GIMG;   // 16 KiB per buffer
+  constexpr unsigned OTILE = 128 * TN * 2;     // epilogue tile, 32 / 16 KiB
+
+  const unsigned nkt = (K + 127) / 128, nnt = (N + TN - 1) / TN;
+  const int k0 = (blockIdx.x % nkt) * 128;     // first row of the dw tile
+  const int n0 = ((blockIdx.x / nkt) % nnt) * TN;
+  const long e = blockIdx.x / (nkt * nnt);
+
+  const int t = threadIdx.x;
+  const int lane = t % WAVE;
+  const int wave = t / WAVE;
+  const int wp = (wave >> 1) * 64;             // wave's dw rows (k index)
+  const int wq = (wave & 1) * (TN / 2);        // wave's dw columns
+  bf16* DW1e = DW1 + e * K * N;
+  bf16* DW3e = PAIR ? DW3 + e * K * N : nullptr;
+
+  const int nsteps = (R + TBR - 1) / TBR;
+  int nlive = nsteps;
+  const unsigned short* live =
+      reinterpret_cast<const unsigned short*>(smem + MOE_TN_LIST);
+  if (valid) {
+    // every wave builds the whole list (the same values to the same
+    // addresses), so each has the count in registers.  A lane takes 16 rows,
+    // two lanes make a step, a pass of the wave covers 32 steps.
+    const unsigned char* ve = valid + e * R;
+    const bool aligned = ((uintptr_t)ve & 15) == 0;
+    unsigned short* list = reinterpret_cast<unsigned short*>(smem + MOE_TN_LIST);
+    nlive = 0;
+    for (int s0 = 0; s0 < nsteps; s0 += 32) {
+      const int r = s0 * TBR + lane * 16;
+      unsigned any = 0;
+      if (aligned && r + 16 <= R) {
+        const uint4 f = *reinterpret_cast<const uint4*>(ve + r);
+        any = f.x | f.y | f.z | f.w;
+      } else {
+        for (int u = 0; u < 16; ++u)
+          if (r + u < R) any |= ve[r + u];
+      }
+      unsigned long long m = __ballot(any != 0);
+      m = (m | (m >> 1)) & 0x5555555555555555ull;   // bit 2s: step s0+s live
+      if ((lane & 1) == 0 && ((m >> lane) & 1))
+        list[nlive + __popcll(m & ((1ull << lane) - 1))] =
+            (unsigned short)(s0 + (lane >> 1));
+      nlive += __popcll(m);
+    }
+    if (nlive == 0) {
+      moe_tile_store<TN>(DW1e, N, k0, n0, K, nullptr, t);
+      if constexpr (PAIR) moe_tile_store<TN>(DW3e, N, k0, n0, K, nullptr, t);
+      return;
+    }
+    __syncthreads();
+  }
+
+  const bf16* Xe = X + e * R * K;
+  const bf16* G1e = G1 + e * R * N;
+  const bf16* G2e = PAIR ? G2 + e * R * N : nullptr;
+
+  // live step i into buffer buf
+  auto stage = [&](int buf, int i) {
+    const int r0 = (valid ? (int)live[i] : i) * TBR;
+    char* dst = smem + buf * BUF;
+    if (r0 + TBR <= R) {
+      tn_stage<256>(Xe, K, r0, k0, K, dst, t, wave);
+      if constexpr (PAIR)
+        tn_stage<128>(wave < 2 ? G1e : G2e, N, r0, n0, N,
+                      dst + XIMG + (wave >> 1) * GIMG, t & 127, wave & 1);
+      else
+        tn_stage<256>(G1e, N, r0, n0, N, dst + XIMG, t, wave);
+    } else {
+      tn_stage_tail<256>(Xe, K, r0, R, k0, K, dst, t);
+      if constexpr (PAIR)
+        tn_stage_tail<128>(wave < 2 ? G1e : G2e, N, r0, R, n0, N,
+                           dst + XIMG + (wave >> 1) * GIMG, t & 127);
+      else
+        tn_stage_tail<256>(G1e, N, r0, R, n0, N, dst + XIMG, t);
+    }
+  };
+
+  f32x4 acc[NP][4][NJ];
+  #pragma unroll
+  for (int p = 0; p < NP; ++p)
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        acc[p][i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  stage(0, 0);
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+
+  for (int it = 0; it < nlive; ++it) {
+    const int buf = it & 1;
+    if (it + 1 < nlive) stage(buf ^ 1, it + 1);
+    const char* img = smem + buf * BUF;
+    bf16x8v x_frag[4], g_frag[NP][NJ];
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      x_frag[i] = tn_frag(img, (wp >> 4) + i, lane);
+    #pragma unroll
+    for (int p = 0; p < NP; ++p)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        g_frag[p][j] = tn_frag(img + XIMG + p * GIMG, (wq >> 4) + j, lane);
+    // transposed product D[n][k]: a lane holds dw row (l&15) and columns
+    // (l>>4)*4 + 0..3 of each 16x16 block
+    #pragma unroll
+    for (int p = 0; p < NP; ++p)
+      #pragma unroll
+      for (int i = 0; i < 4; ++i)
+        #pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          acc[p][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              g_frag[p][j], x_frag[i], acc[p][i][j], 0, 0, 0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+  }
+
+  #pragma unroll
+  for (int p = 0; p < NP; ++p)
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        moe_tile_put<TN>(smem + p * OTILE, wp + i * 16 + (lane & 15),
+                         wq + j * 16 + (lane >> 4) * 4, acc[p][i][j]);
+  __syncthreads();
+  moe_tile_store<TN>(DW1e, N, k0, n0, K, smem, t);
+  if constexpr (PAIR) moe_tile_store<TN>(DW3e, N, k0, n0, K, smem + OTILE, t);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+moe_tn_kernel(const bf16* __restrict__ X, const bf16* __restrict__ G,
+              bf16* __restrict__ DW, const unsigned char* __restrict__ valid,
+              int R, int K, int N) {
+  moe_tn_body<false>(X, G, nullptr, DW, nullptr, valid, R, K, N);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+moe_tn2_kernel(const bf16* __restrict__ X, const bf16* __restrict__ G1,
+               const bf16* __restrict__ G2, bf16* __restrict__ DW1,
+               bf16* __restrict__ DW3, const unsigned char* __restrict__ valid,
+               int R, int K, int N) {
+  moe_tn_body<true>(X, G1, G2, DW1, DW3, valid, R, K, N);
+}
+
 
 // ===========================================================================
 // host wrappers
@@ -1217,4 +1578,109 @@ moe_expert_up(const at::Tensor& x, const at::Tensor& w1, const at::Tensor& w3,
       (const bf16*)w3.data_ptr(), (bf16*)h.data_ptr(), (bf16*)a.data_ptr(),
       (bf16*)b.data_ptr(), moe_nn_valid(valid), (int)s.R, (int)s.K, (int)s.N);
   return {h, a, b};
+}
+
+// ---------------------------------------------------------------------------
+// MoE expert FFN backward (moe_nt / moe_tn kernels)
+// ---------------------------------------------------------------------------
+static void moe_bwd_valid(const std::optional<at::Tensor>& valid, long E,
+                          long R) {
+  if (valid)
+    TORCH_CHECK(valid->is_cuda() && valid->dtype() == at::kBool &&
+                valid->is_contiguous() && valid->dim() == 2 &&
+                valid->size(0) == E && valid->size(1) == R,
+                "moe_expert: valid must be a contiguous bool [E,R]");
+}
+
+static unsigned moe_bwd_grid(long e, long tiles_a, long tiles_b) {
+  const long nwg = e * tiles_a * tiles_b;
+  TORCH_CHECK(nwg < (1L << 31), "moe_expert: too many tiles for one launch");
+  return (unsigned)nwg;
+}
+
+// dx = g1 @ w1^T (+ g2 @ w2^T): g [E,R,N], w [E,K,N] -> [E,R,K]
+at::Tensor moe_expert_dx(const at::Tensor& g1, const at::Tensor& w1,
+                         const std::optional<at::Tensor>& g2,
+                         const std::optional<at::Tensor>& w2,
+                         const std::optional<at::Tensor>& valid) {
+  TORCH_CHECK(g1.dim() == 3 && w1.dim() == 3,
+              "moe_expert_dx: g [E,R,N], w [E,K,N]");
+  TORCH_CHECK(g2.has_value() == w2.has_value(),
+              "moe_expert_dx: g2 and w2 come together");
+  const long E = g1.size(0), R = g1.size(1), N = g1.size(2), K = w1.size(1);
+  TORCH_CHECK(E >= 1 && R >= 1 && N >= NN_BK && N % NN_BK == 0 && K >= 8 &&
+              K % 8 == 0, "moe_expert_dx: E, R >= 1, N % 32 == 0, K % 8 == 0");
+  TORCH_CHECK(R < (1L << 31) && K < (1L << 31) && N < (1L << 31));
+  moe_nn_operand(g1, {E, R, N}, "g1");
+  moe_nn_operand(w1, {E, K, N}, "w1");
+  if (g2) {
+    moe_nn_operand(*g2, {E, R, N}, "g2");
+    moe_nn_operand(*w2, {E, K, N}, "w2");
+  }
+  moe_bwd_valid(valid, E, R);
+  const unsigned grid =
+      moe_bwd_grid(E, (R + NN_BM - 1) / NN_BM, (K + 127) / 128);
+  auto dx = at::empty({E, R, K}, g1.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (g2)
+    hipLaunchKernelGGL(moe_nt2_kernel, dim3(grid), dim3(256), 32768, stream,
+        (const bf16*)g1.data_ptr(), (const bf16*)w1.data_ptr(),
+        (const bf16*)g2->data_ptr(), (const bf16*)w2->data_ptr(),
+        (bf16*)dx.data_ptr(), moe_nn_valid(valid), (int)R, (int)K, (int)N);
+  else
+    hipLaunchKernelGGL(moe_nt_kernel, dim3(grid), dim3(256), 32768, stream,
+        (const bf16*)g1.data_ptr(), (const bf16*)w1.data_ptr(),
+        (bf16*)dx.data_ptr(), moe_nn_valid(valid), (int)R, (int)K, (int)N);
+  return dx;
+}
+
+struct MoeTnShape { long E, R, K, N; unsigned lds; };
+
+static MoeTnShape moe_tn_shape(const at::Tensor& x, const at::Tensor& g,
+                               const std::optional<at::Tensor>& valid) {
+  TORCH_CHECK(x.dim() == 3 && g.dim() == 3,
+              "moe_expert_dw: x [E,R,K], g [E,R,N]");
+  MoeTnShape s{x.size(0), x.size(1), x.size(2), g.size(2), MOE_TN_LIST};
+  const long nsteps = (s.R + TBR - 1) / TBR;
+  TORCH_CHECK(s.E >= 1 && s.R >= 1 && s.K >= 8 && s.K % 8 == 0 && s.N >= 8 &&
+              s.N % 8 == 0 && nsteps <= 4096,
+              "moe_expert_dw: E, R >= 1, K % 8 == 0, N % 8 == 0, "
+              "R <= 131072");
+  TORCH_CHECK(s.K < (1L << 31) && s.N < (1L << 31));
+  moe_nn_operand(x, {s.E, s.R, s.K}, "x");
+  moe_nn_operand(g, {s.E, s.R, s.N}, "g");
+  moe_bwd_valid(valid, s.E, s.R);
+  if (valid)     // the live-step list, one uint16 per 32-row step
+    s.lds += (unsigned)((2 * nsteps + 15) / 16 * 16);
+  return s;
+}
+
+// dw = x^T @ g: x [E,R,K], g [E,R,N] -> [E,K,N]
+at::Tensor moe_expert_dw(const at::Tensor& x, const at::Tensor& g,
+                         const std::optional<at::Tensor>& valid) {
+  const MoeTnShape s = moe_tn_shape(x, g, valid);
+  const unsigned grid = moe_bwd_grid(s.E, (s.K + 127) / 128, (s.N + 127) / 128);
+  auto dw = at::empty({s.E, s.K, s.N}, x.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(moe_tn_kernel, dim3(grid), dim3(256), s.lds, stream,
+      (const bf16*)x.data_ptr(), (const bf16*)g.data_ptr(),
+      (bf16*)dw.data_ptr(), moe_nn_valid(valid), (int)s.R, (int)s.K, (int)s.N);
+  return dw;
+}
+
+// (dw1, dw3) = (x^T @ g1, x^T @ g2), the x image staged once for both
+std::tuple<at::Tensor, at::Tensor>
+moe_expert_dw2(const at::Tensor& x, const at::Tensor& g1, const at::Tensor& g2,
+               const std::optional<at::Tensor>& valid) {
+  const MoeTnShape s = moe_tn_shape(x, g1, valid);
+  moe_nn_operand(g2, {s.E, s.R, s.N}, "g2");
+  const unsigned grid = moe_bwd_grid(s.E, (s.K + 127) / 128, (s.N + 63) / 64);
+  auto dw1 = at::empty({s.E, s.K, s.N}, x.options());
+  auto dw3 = at::empty_like(dw1);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(moe_tn2_kernel, dim3(grid), dim3(256), s.lds, stream,
+      (const bf16*)x.data_ptr(), (const bf16*)g1.data_ptr(),
+      (const bf16*)g2.data_ptr(), (bf16*)dw1.data_ptr(), (bf16*)dw3.data_ptr(),
+      moe_nn_valid(valid), (int)s.R, (int)s.K, (int)s.N);
+  return {dw1, dw3};
 }
