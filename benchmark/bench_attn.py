@@ -23,7 +23,8 @@ run_ragged); without it the output is what it always was.  --kv-heads N
 times grouped-query attention against the expand-and-reduce a build
 without the GQA kernels needs (see run_gqa).  --window W times
 sliding-window causal attention against the causal kernels on the same
-tensors (see run_window).
+tensors (see run_window).  --doc-len L does the same for document-masked
+attention of S / L equal packed documents (see run_doc).
 """
 import argparse
 import json
@@ -237,8 +238,60 @@ def run_window(args, ext):
         print(json.dumps(r), flush=True)
 
 
+def run_doc(args, ext):
+    """--doc-len L: document-masked causal attention of S / L equal
+    documents packed into each row, forward and backward timed apart against
+    the causal kernels on the same tensors, the two alternated inside each
+    repeat.  Shapes from --bhsd (B,H,S,D[,Hkv]).  pair_ratio is the (q, key)
+    pairs the mask leaves over the causal count, (S/L) L(L+1)/2 over
+    S(S+1)/2: what the time ratio would reach if tiles were free to skip at
+    any grain."""
+    L = args.doc_len
+    for s in args.bhsd.split(";"):
+        B, H, S, D, *kvh = (int(x) for x in s.split(","))
+        assert S % L == 0, f"--doc-len {L} does not divide S = {S}"
+        Hkv = kvh[0] if kvh else H
+        bf = torch.bfloat16
+        q = torch.randn(B, H, S, D, device="cuda", dtype=bf)
+        k = torch.randn(B, Hkv, S, D, device="cuda", dtype=bf)
+        v = torch.randn_like(k)
+        g = torch.randn_like(q)
+        from easydist_amd.ops.attention import document_bounds
+        ids = (torch.arange(S, device="cuda") // L).expand(B, S)
+        steps = {}
+        for name, doc in (("causal", ()),
+                          ("doc", (None,) + document_bounds(ids))):
+            o, lse = ext.flash_attn_fwd(q, k, v, True, *doc)
+            steps[name] = (
+                lambda doc=doc: ext.flash_attn_fwd(q, k, v, True, *doc),
+                lambda doc=doc, o=o, lse=lse: ext.flash_attn_bwd(
+                    g, q, k, v, o, lse, True, *doc))
+        t = {n: ([], []) for n in steps}
+        for fwd, bwd in steps.values():
+            time_ms(fwd, args.warm_iters, 0)
+            time_ms(bwd, args.warm_iters, 0)
+        for _ in range(args.repeats):
+            for n, (fwd, bwd) in steps.items():   # alternate inside a repeat
+                t[n][0].append(time_ms(fwd, args.iters))
+                t[n][1].append(time_ms(bwd, args.iters))
+        med = statistics.median
+        r = {"shape": f"B{B} H{H} S{S} D{D}"
+             + (f" Hkv{Hkv}" if Hkv != H else ""), "doc_len": L,
+             "fwd_ms": {n: stats(t[n][0]) for n in t},
+             "bwd_ms": {n: stats(t[n][1]) for n in t},
+             "fwd_ratio": med(t["doc"][0]) / med(t["causal"][0]),
+             "bwd_ratio": med(t["doc"][1]) / med(t["causal"][1]),
+             "pair_ratio": (L + 1) / (S + 1)}
+        print(json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--doc-len", type=int, default=0,
+                    help="time document-masked causal attention of S / L "
+                         "equal documents of this length against the causal "
+                         "kernels on the same tensors (see run_doc); shapes "
+                         "from --bhsd")
     ap.add_argument("--window", type=int, default=0,
                     help="time sliding-window causal attention of this "
                          "window against the causal kernels on the same "
@@ -290,6 +343,9 @@ def main():
     if args.window:
         assert args.bhsd, "--window takes its shapes from --bhsd"
         return run_window(args, ext)
+    if args.doc_len:
+        assert args.bhsd, "--doc-len takes its shapes from --bhsd"
+        return run_doc(args, ext)
     causals = {"0": [False], "1": [True], "both": [True, False]}[args.causal]
     pick = {"0": ["0"], "1": ["1"], "both": ["0", "1"], "env": [None]}
     # a configuration is a (map, tr, dkv geometry) triple

@@ -47,6 +47,14 @@ def _flops_of(node: fx.Node) -> float:
         if t in (ed.flash_attention_bwd.default,):
             q = shape(1)
             return 2.0 * q[0] * q[1] * q[2] * q[2] * q[3] * 5 * 0.5
+        if t in (ed.flash_attention_doc.default,
+                 ed.flash_attention_doc_bwd.default):
+            # the causal formulas as an upper bound: the pair count is the
+            # sum of L^2 / 2 over the document lengths, which is data
+            fwd = t is ed.flash_attention_doc.default
+            q = shape(0 if fwd else 1)
+            return 2.0 * q[0] * q[1] * q[2] * q[2] * q[3] * (2 if fwd else 5) \
+                * 0.5
         if t in (ed.flash_attention_swa.default,
                  ed.flash_attention_swa_bwd.default):
             # the causal formulas with S*S/2 replaced by the band's pair

@@ -768,6 +768,33 @@ def _register_custom_ops():
     register_preset(ed.flash_attention_swa.default)(_swa_rule(3, 2))
     register_preset(ed.flash_attention_swa_bwd.default)(_swa_rule(6, 3))
 
+    def _doc_rule(n_in, n_out):
+        # flash_attention_doc (q, k, v, lo, hi) and flash_attention_doc_bwd
+        # (grad, q, k, v, out, lse, lo, hi): the n_in tensors before the
+        # bounds shard on the batch and head dims as in _swa_rule.  lo and hi
+        # are [B, S]: they shard with the batch and stay replicated under a
+        # head split (their dim 1 is the sequence, which never shards; no
+        # RUNTIME_REALIZED entry, ring attention does not know documents).
+        iq = 0 if n_in == 3 else 1          # q; k follows it
+        def rule(input_shapes, args, kwargs):
+            if len(input_shapes) < n_in + 2 or len(input_shapes[iq]) != 4:
+                return None, {}
+            ann = ShardAnnotation.init_from_input_shapes(input_shapes)
+            combs = {}
+            sid = 1
+            for d in (0, 1):
+                if input_shapes[iq][d] <= 1 or input_shapes[iq + 1][d] <= 1:
+                    continue
+                for i in range(n_in + (2 if d == 0 else 0)):
+                    ann[i][d] = ShardDim.get_shard_dim(sid)
+                combs[sid] = [_gather(d)] * n_out
+                sid += 1
+            return ann, combs
+        return rule
+
+    register_preset(ed.flash_attention_doc.default)(_doc_rule(3, 2))
+    register_preset(ed.flash_attention_doc_bwd.default)(_doc_rule(6, 3))
+
     @register_preset(ed.rope_qkv.default)
     def _rope_rule(input_shapes, args, kwargs):
         # (qkv [B,S,W], cos [S,D/2], sin [S,D/2]) -> out [B,S,W]: every row

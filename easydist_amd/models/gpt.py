@@ -81,9 +81,10 @@ class CausalSelfAttention(nn.Module):
                                 bias=cfg.bias)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd, bias=cfg.bias)
 
-    def forward(self, x, rope=None):
+    def forward(self, x, rope=None, doc=None):
         """rope: the (cos, sin) tables [T, hd/2] of this rank's positions,
-        or None for no rotation."""
+        or None for no rotation.  doc: the (lo, hi) document bounds of
+        packed sequences (ops.attention.document_bounds), or None."""
         from ..ops import attention, ring_attention
         B, T, C = x.shape
         qkv = self.c_attn(x)
@@ -102,7 +103,15 @@ class CausalSelfAttention(nn.Module):
         q = q.view(B, T, self.n_head, hd).transpose(1, 2)
         k = k.view(B, T, self.n_kv_head, hd).transpose(1, 2)
         v = v.view(B, T, self.n_kv_head, hd).transpose(1, 2)
-        if self.sp_group is not None:
+        if doc is not None:
+            if self.sp_group is not None or self.sliding_window is not None:
+                raise NotImplementedError(
+                    "document bounds with sequence parallelism or "
+                    "sliding_window: neither ring attention nor the window "
+                    "kernels know documents")
+            y = attention.scaled_dot_product_attention(
+                q, k, v, causal=True, doc_bounds=doc)
+        elif self.sp_group is not None:
             if self.sliding_window is not None:
                 raise NotImplementedError(
                     "sliding_window with sequence parallelism: ring "
@@ -152,10 +161,21 @@ class Block(nn.Module):
         self.ln_2 = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
         self.mlp = MLPBlock(cfg)
 
-    def forward(self, x, rope=None):
-        x = x + self.attn(self.ln_1(x), rope)
+    def forward(self, x, rope=None, doc=None):
+        x = x + self.attn(self.ln_1(x), rope, doc)
         x = x + self.mlp(self.ln_2(x))
         return x
+
+
+def packed_document_bounds(cfg, doc_ids, sp_group=None):
+    """The (lo, hi) bounds of doc_ids [B, T] for a model's forward: computed
+    once there, shared by every layer."""
+    if sp_group is not None or cfg.sliding_window is not None:
+        raise NotImplementedError(
+            "doc_ids with sequence parallelism or sliding_window: neither "
+            "ring attention nor the window kernels know documents")
+    from ..ops.attention import document_bounds
+    return document_bounds(doc_ids)
 
 
 def register_rope_tables(module, block_size, head_dim, base):
@@ -210,16 +230,27 @@ class GPT(nn.Module):
             blk.attn.sp_group = group
         return self
 
-    def forward(self, idx):
+    def forward(self, idx, doc_ids=None):
+        """doc_ids [B, T]: integer ids of packed sequences, constant on each
+        document and changing at each boundary; a token then attends the
+        earlier tokens of its own document only.  None: plain causal."""
         B, T = idx.shape
         off = getattr(self, "_sp_rank", 0) * T \
             if getattr(self, "_sp_group", None) is not None else 0
-        rope = None
+        rope = doc = None
+        if doc_ids is not None:
+            doc = packed_document_bounds(self.cfg, doc_ids,
+                                         getattr(self, "_sp_group", None))
         if self.cfg.rope:
             # positions enter through q and k: a sequence shard takes its
-            # own rows of the tables
+            # own rows of the tables.  With doc_ids they stay as they are:
+            # a rotary score depends on i - j only, so within a document
+            # nothing changes when positions do not restart.
             x = self.wte(idx)
             rope = (self.rope_cos[off:off + T], self.rope_sin[off:off + T])
+        elif doc is not None:
+            # learned positions restart at each document's first token
+            x = self.wte(idx) + self.wpe(self.pos[:T] - doc[0])
         else:
             x = self.wte(idx) + self.wpe(self.pos[off:off + T])
         if torch.is_autocast_enabled(x.device.type):
@@ -228,12 +259,12 @@ class GPT(nn.Module):
             # pair around every matmul)
             x = x.to(torch.bfloat16)
         for blk in self.h:
-            x = blk(x, rope)
+            x = blk(x, rope, doc)
         x = self.ln_f(x)
         return self.lm_head(x)
 
-    def loss(self, idx, targets):
-        logits = self(idx)
+    def loss(self, idx, targets, doc_ids=None):
+        logits = self(idx, doc_ids)
         return F.cross_entropy(logits.view(-1, logits.size(-1)),
                                targets.reshape(-1))
 

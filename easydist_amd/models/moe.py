@@ -190,8 +190,8 @@ class MoEBlock(nn.Module):
         self.ln_2 = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
         self.moe = MoELayer(cfg, ep_group)
 
-    def forward(self, x, rope=None):
-        x = x + self.attn(self.ln_1(x), rope)
+    def forward(self, x, rope=None, doc=None):
+        x = x + self.attn(self.ln_1(x), rope, doc)
         x = x + self.moe(self.ln_2(x))
         return x
 
@@ -220,22 +220,28 @@ class MoEGPT(nn.Module):
             nn.init.normal_(self.wpe.weight, std=0.02)
         nn.init.normal_(self.lm_head.weight, std=0.02)
 
-    def forward(self, idx):
+    def forward(self, idx, doc_ids=None):
+        """doc_ids [B, T]: packed sequences, as GPT.forward."""
         B, T = idx.shape
-        rope = None
+        rope = doc = None
+        if doc_ids is not None:
+            from .gpt import packed_document_bounds
+            doc = packed_document_bounds(self.cfg, doc_ids)
         if self.cfg.rope:
             x = self.wte(idx)
             rope = (self.rope_cos[:T], self.rope_sin[:T])
+        elif doc is not None:
+            x = self.wte(idx) + self.wpe(self.pos[:T] - doc[0])
         else:
             x = self.wte(idx) + self.wpe(self.pos[:T])
         if torch.is_autocast_enabled(x.device.type):
             x = x.to(torch.bfloat16)   # keep the residual stream bf16
         for blk in self.h:
-            x = blk(x, rope)
+            x = blk(x, rope, doc)
         return self.lm_head(self.ln_f(x))
 
-    def loss(self, idx, targets):
-        logits = self(idx)
+    def loss(self, idx, targets, doc_ids=None):
+        logits = self(idx, doc_ids)
         return F.cross_entropy(logits.float().view(-1, logits.size(-1)),
                                targets.reshape(-1))
 

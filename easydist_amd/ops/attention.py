@@ -22,6 +22,17 @@ keys with itself.  The window instantiations of the same three kernels walk
 only the tiles the band touches, O(S * W) with no mask tensor; W >= S is
 plain causal attention and runs the causal kernels.  The packed backward and
 the sequence-parallel (ring) rewrite do not know windows yet.
+
+`flash_attention_doc` is document-masked causal self-attention for packed
+sequences: a row of S tokens holds several documents and token i attends
+only the earlier tokens of its own, keys lo[b, i] <= j <= i.  The bounds are
+two int32 [B, S] tensors from `document_bounds(doc_ids)`, computed once per
+step and shared by all layers and heads; there is no [S, S] mask.  The
+document instantiations of the same three kernels walk only the tiles a
+block's documents touch: the sum of L_k^2 / 2 pairs over the document
+lengths L_k in place of S^2 / 2.  The launches never read the bounds on the
+host.  The packed backward and ring attention do not know documents, and a
+window inside documents is not offered.
 """
 from __future__ import annotations
 
@@ -51,6 +62,33 @@ lib.define("flash_attention_swa(Tensor q, Tensor k, Tensor v, int window) "
 lib.define("flash_attention_swa_bwd(Tensor grad, Tensor q, Tensor k, "
            "Tensor v, Tensor out, Tensor lse, int window) "
            "-> (Tensor, Tensor, Tensor)")
+# document-masked causal attention (packed sequences): ops of their own for
+# the same reason; lo and hi are the int32 [B, S] bounds of document_bounds
+lib.define("flash_attention_doc(Tensor q, Tensor k, Tensor v, Tensor lo, "
+           "Tensor hi) -> (Tensor, Tensor)")
+lib.define("flash_attention_doc_bwd(Tensor grad, Tensor q, Tensor k, "
+           "Tensor v, Tensor out, Tensor lse, Tensor lo, Tensor hi) "
+           "-> (Tensor, Tensor, Tensor)")
+
+
+def document_bounds(doc_ids):
+    """(lo, hi) int32 [B, S] of integer ids [B, S] that are constant on each
+    document and change at each boundary: lo[b, i] is the first token of the
+    document of token i, hi[b, i] one past its last.  Compute it once per
+    step; every layer and head shares it."""
+    if doc_ids.dim() != 2:
+        raise ValueError("document_bounds: doc_ids must be [B, S], got "
+                         f"{tuple(doc_ids.shape)}")
+    B, S = doc_ids.shape
+    pos = torch.arange(S, device=doc_ids.device)
+    edge = doc_ids[:, 1:] != doc_ids[:, :-1]        # token i + 1 starts one
+    first = torch.ones(B, 1, dtype=torch.bool, device=doc_ids.device)
+    # the latest start at or before i; the earliest end after i
+    start = torch.where(torch.cat([first, edge], 1), pos, 0)
+    lo = torch.cummax(start, dim=1).values
+    end = torch.where(torch.cat([edge, first], 1), pos + 1, S)
+    hi = torch.cummin(end.flip(1), dim=1).values.flip(1)
+    return lo.to(torch.int32), hi.to(torch.int32)
 
 
 def _group(q, k, v):
@@ -99,13 +137,35 @@ def _check_window(q, k, window):
                          f"Sq {q.shape[-2]} and Sk {k.shape[-2]}")
 
 
-def _math_fwd(q, k, v, causal, window=None):
-    # q: [B, H, S, D]; k,v: [B, Hkv, T, D]; a window implies causal
+def _doc_mask(lo, S):
+    """[B, 1, S, S], True = visible: lo[b, i] <= j <= i."""
+    j = torch.arange(S, device=lo.device)
+    return ((j[None, None, :] >= lo[:, :, None])
+            & (j[None, None, :] <= j[None, :, None])).unsqueeze(1)
+
+
+def _check_doc(q, k, lo, hi):
+    if q.dim() != 4 or q.shape[-2] != k.shape[-2]:
+        raise ValueError("flash_attention_doc: 4-D self-attention only, got "
+                         f"q {tuple(q.shape)} and k {tuple(k.shape)}")
+    want = (q.shape[0], q.shape[2])
+    for t in (lo, hi):
+        if t.dtype != torch.int32 or tuple(t.shape) != want:
+            raise ValueError(
+                f"flash_attention_doc: lo and hi must be int32 {want}, got "
+                f"{t.dtype} {tuple(t.shape)}")
+
+
+def _math_fwd(q, k, v, causal, window=None, doc=None):
+    # q: [B, H, S, D]; k,v: [B, Hkv, T, D]; a window implies causal; doc =
+    # (lo, hi) implies causal and replaces the mask by lo[b, i] <= j <= i
     G = _group(q, k, v)
     k, v = _expand_kv(k, G), _expand_kv(v, G)
     scale = 1.0 / math.sqrt(q.shape[-1])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
-    if causal:
+    if doc is not None:
+        s = s.masked_fill(~_doc_mask(doc[0], s.shape[-1]), float("-inf"))
+    elif causal:
         mask = _mask(s.shape[-2], s.shape[-1], window, s.device)
         s = s.masked_fill(~mask, float("-inf"))
     lse = torch.logsumexp(s, dim=-1)
@@ -114,13 +174,15 @@ def _math_fwd(q, k, v, causal, window=None):
     return out, lse
 
 
-def _math_bwd(grad, q, k, v, out, lse, causal, window=None):
+def _math_bwd(grad, q, k, v, out, lse, causal, window=None, doc=None):
     G = _group(q, k, v)
     kdt, vdt = k.dtype, v.dtype
     k, v = _expand_kv(k, G), _expand_kv(v, G)
     scale = 1.0 / math.sqrt(q.shape[-1])
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
-    if causal:
+    if doc is not None:
+        s = s.masked_fill(~_doc_mask(doc[0], s.shape[-1]), float("-inf"))
+    elif causal:
         mask = _mask(s.shape[-2], s.shape[-1], window, s.device)
         s = s.masked_fill(~mask, float("-inf"))
     p = torch.exp(s - lse.unsqueeze(-1).float())
@@ -206,6 +268,38 @@ def _swa_bwd_cuda(grad, q, k, v, out, lse, window):
     return _math_bwd(grad, q, k, v, out, lse, True, window)
 
 
+def _doc_fwd_cpu(q, k, v, lo, hi):
+    _check_doc(q, k, lo, hi)
+    return _math_fwd(q, k, v, True, None, (lo, hi))
+
+
+def _doc_fwd_cuda(q, k, v, lo, hi):
+    _check_doc(q, k, lo, hi)
+    ext = load_extension()
+    if ext is not None and _kernel_ok(q, k, v):
+        return ext.flash_attn_fwd(q, k, v, True, None, lo.contiguous(),
+                                  hi.contiguous())
+    from . import require_hip_ops
+    if _kernel_ok(q, k, v):
+        require_hip_ops()   # raises when the extension should exist
+    return _math_fwd(q, k, v, True, None, (lo, hi))
+
+
+def _doc_bwd_cpu(grad, q, k, v, out, lse, lo, hi):
+    _check_doc(q, k, lo, hi)
+    return _math_bwd(grad, q, k, v, out, lse, True, None, (lo, hi))
+
+
+def _doc_bwd_cuda(grad, q, k, v, out, lse, lo, hi):
+    _check_doc(q, k, lo, hi)
+    ext = load_extension()
+    if ext is not None and _kernel_ok(q, k, v):
+        return ext.flash_attn_bwd(grad, q, k, v, out.contiguous(),
+                                  lse.contiguous(), True, None,
+                                  lo.contiguous(), hi.contiguous())
+    return _math_bwd(grad, q, k, v, out, lse, True, None, (lo, hi))
+
+
 def _pack3(dq, dk, dv):
     B, _, S, D = dq.shape
     return torch.cat([d.transpose(1, 2).reshape(B, S, d.shape[1] * D)
@@ -234,6 +328,10 @@ lib.impl("flash_attention_swa", _swa_fwd_cpu, "CPU")
 lib.impl("flash_attention_swa", _swa_fwd_cuda, "CUDA")
 lib.impl("flash_attention_swa_bwd", _swa_bwd_cpu, "CPU")
 lib.impl("flash_attention_swa_bwd", _swa_bwd_cuda, "CUDA")
+lib.impl("flash_attention_doc", _doc_fwd_cpu, "CPU")
+lib.impl("flash_attention_doc", _doc_fwd_cuda, "CUDA")
+lib.impl("flash_attention_doc_bwd", _doc_bwd_cpu, "CPU")
+lib.impl("flash_attention_doc_bwd", _doc_bwd_cuda, "CUDA")
 
 
 @torch.library.register_fake("easydist_amd::flash_attention")
@@ -264,6 +362,16 @@ def _swa_fake(q, k, v, window):
 
 @torch.library.register_fake("easydist_amd::flash_attention_swa_bwd")
 def _swab_fake(grad, q, k, v, out, lse, window):
+    return _fab_fake(grad, q, k, v, out, lse, True)
+
+
+@torch.library.register_fake("easydist_amd::flash_attention_doc")
+def _doc_fake(q, k, v, lo, hi):
+    return _fa_fake(q, k, v, True)
+
+
+@torch.library.register_fake("easydist_amd::flash_attention_doc_bwd")
+def _docb_fake(grad, q, k, v, out, lse, lo, hi):
     return _fab_fake(grad, q, k, v, out, lse, True)
 
 
@@ -303,10 +411,41 @@ torch.library.register_autograd("easydist_amd::flash_attention_swa",
                                 _swa_backward, setup_context=_swa_setup_ctx)
 
 
+def _doc_backward(ctx, grad_out, grad_lse):
+    q, k, v, out, lse, lo, hi = ctx.saved_tensors
+    dq, dk, dv = torch.ops.easydist_amd.flash_attention_doc_bwd(
+        grad_out, q, k, v, out, lse, lo, hi)
+    return dq, dk, dv, None, None      # the integer bounds take no gradient
+
+
+def _doc_setup_ctx(ctx, inputs, output):
+    q, k, v, lo, hi = inputs
+    out, lse = output
+    ctx.save_for_backward(q, k, v, out, lse, lo, hi)
+
+
+torch.library.register_autograd("easydist_amd::flash_attention_doc",
+                                _doc_backward, setup_context=_doc_setup_ctx)
+
+
 def scaled_dot_product_attention(q, k, v, causal: bool = True,
-                                 window: Optional[int] = None):
+                                 window: Optional[int] = None,
+                                 doc_bounds: Optional[Tuple] = None):
     """window = W: sliding-window causal attention, row i attends keys
-    i - W + 1 .. i (flash_attention_swa); it needs causal=True."""
+    i - W + 1 .. i (flash_attention_swa); it needs causal=True.
+    doc_bounds = (lo, hi) from document_bounds: packed sequences, row i
+    attends keys lo[b, i] .. i (flash_attention_doc); it needs causal=True
+    and no window."""
+    if doc_bounds is not None:
+        if not causal:
+            raise ValueError("scaled_dot_product_attention: doc_bounds needs "
+                             "causal=True")
+        if window is not None:
+            raise ValueError("scaled_dot_product_attention: doc_bounds and a "
+                             "window do not combine")
+        lo, hi = doc_bounds
+        out, _ = torch.ops.easydist_amd.flash_attention_doc(q, k, v, lo, hi)
+        return out
     if window is not None:
         if not causal:
             raise ValueError("scaled_dot_product_attention: a window needs "

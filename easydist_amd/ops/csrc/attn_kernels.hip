@@ -200,6 +200,72 @@ DEVINL bool band_ok(int key, int qrow, int W) {
   return (unsigned)(qrow - key) < (unsigned)W;
 }
 
+// ---- DOC: document-masked causal attention (packed sequences) ---------------
+// A row of S tokens packs several documents and query row i attends key j iff
+// lo[b, i] <= j <= i: the WIN band with a left edge per row.  LO and HI are
+// int32 [B, S], the same for every head: lo[b, i] is the first token of the
+// document of token i and hi[b, j] one past the last token of the document of
+// token j, both non-decreasing along S.  DOC = false is the code as it was
+// measured: the two pointers are never read and every added test sits under
+// `if constexpr` or folds away, as for WIN = false.  DOC is always causal and
+// never combined with WIN; the launch code never looks at the bounds' values
+// (no host synchronisation, so the launches record into a captured graph).
+// DOC exists in the default forms only (fwd and dq TR = 1, dkv SW = 0 and
+// TR = ATTN_TR_DKV(D, NW)) and with RAGGED = true only: S % 128 == 0 runs
+// the ragged form too, which differs by one v_min per row index of a global
+// load.  That halves the count to 4 fwd, 4 dq and 8 dkv instantiations (D in
+// {64, 128}, with and without GQA, both dkv geometries); their VGPRs are
+// listed in profiles/README.md (Round 16).
+// A bound is read with its index clamped as rag_row clamps, and its value is
+// clamped to [0, i] (lo) or [j + 1, S] (hi): malformed bounds give wrong
+// numbers but never a tile or an address out of range.
+// The tile loops stay block-uniform and only their bounds move:
+//   fwd, dq: the q block at qb0 walks kv tiles lo[qb0] / KB (lo is
+//     non-decreasing, so the block's first row has the smallest bound; one
+//     scalar load per workgroup) up to the causal end.  The first tile can
+//     be odd: buffer t & 1 as under WIN.  A lane owns one q row and keeps
+//     W_row = qrow - lo[qrow] + 1 in one VGPR, so the mask is
+//     band_ok(key, qrow, W_row), the one compare WIN pays.  A wave skips the
+//     MFMA work of a tile wholly left of lo at its first row qr0 (lane 0's
+//     value, made scalar by readfirstlane) and still reaches every barrier.
+//     The per-element compares run per LANE, as before: a row takes them in
+//     a tile cut by the diagonal, the sequence end or its own left bound,
+//     which is finer than the wave's last row and costs the same.  The
+//     forward's m_ref covers a leading tile masked whole for some rows.
+//   dkv: the key block at kb0 walks q tiles from kb0 to
+//     hi[min(kb0 + KBLK - 1, S - 1)], per query head under GQA.  In the
+//     strip form a lane holds one q column per fragment and four keys, and
+//     already loads lse per q column: lo of that column is one more load
+//     beside it and no register that lives across tiles, where hi of the
+//     lane's four keys would be four in kernels that sit at 254 and 256
+//     VGPRs.  So the element test is lo[qcol] <= key <= qcol through
+//     band_ok, and a masked P is an exact zero.  A tile takes the compares
+//     when it reaches past hi of the wave's FIRST key (the wave's smallest):
+//     below it every q of the tile is in the document of every key of the
+//     wave that the causal test lets through.  The causal wave skip stays;
+//     a right-edge skip for whole waves would need hi of the wave's last key
+//     in a register of its own and is not taken.
+// attn_block_map is unchanged.  Work per block now depends on the data (a
+// block does between one tile and its causal count), so the causal balance
+// across XCDs is an approximation under DOC; nobody has measured it.
+struct DocBand { int w, lo_w, lo_b; };
+// lo of row i, index and value clamped
+DEVINL int doc_lo(const int* lo, int i, int S) {
+  i = min(i, S - 1);
+  return min(max(lo[i], 0), i);
+}
+// band width of q row (or column) qrow: keys lo .. qrow
+DEVINL int doc_width(const int* lo, int qrow, int S) {
+  return qrow - doc_lo(lo, qrow, S) + 1;
+}
+// fwd and dq: the lane's band width, lo of the wave's first row (lane 0
+// owns it) and lo of the block's first row.  Call with EXEC all ones.
+DEVINL DocBand doc_band(const int* lo, int qrow, int qb0, int S) {
+  const int w = doc_width(lo, qrow, S);
+  return {w, __builtin_amdgcn_readfirstlane(qrow - w + 1),
+          doc_lo(lo, qb0, S)};
+}
+
 // ---- shared pieces of the swapped-operand (S^T) form ----------------------
 // pack a C-layout f32 fragment row-pair into bf16x2 words
 DEVINL void swp_pack(const f32x4* sacc, int nj, unsigned pk[][2]) {
@@ -248,7 +314,7 @@ DEVINL bf16x8v swp_butterfly(const unsigned pk[][2], int ks, int fg) {
 // strip form, a 256-row (two fragments per wave) block and direct-from-L2
 // K reads were all A/B'd on hardware and lost (profiles/README.md).
 template <int D, bool TR, bool RAGGED = false, bool GQA = false,
-          bool WIN = false>
+          bool WIN = false, bool DOC = false>
 __global__ void
 // waves/SIMD floor.  The aligned D = 64 kernel fits 5 (96 VGPRs); the
 // clamped row index costs the ragged one 4 more, so it runs at 4: a floor
@@ -259,8 +325,11 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                  float* __restrict__ LSE, int B, int H, int S, bool causal,
                  float scale,
                  long qsb, long qsh, long qss, long ksb, long ksh, long kss,
-                 long vsb, long vsh, long vss, int map_mode, int G, int W) {
+                 long vsb, long vsh, long vss, int map_mode, int G, int W,
+                 const int* __restrict__ LO, const int* __restrict__ HI) {
   static_assert(!WIN || TR, "the window kernels are instantiated for TR = 1");
+  static_assert(!DOC || (TR && RAGGED && !WIN),
+                "the document kernels are TR = 1, RAGGED, and not WIN");
   // grid: 1-D, ceil(S/QBLK) * B*H workgroups placed by attn_block_map
   // (attn_block_map.h); 8 waves of one 16-row fragment each.  The round-1
   // 4-wave/256-thread form ran ONE wave per SIMD (110 KB LDS) — every
@@ -300,6 +369,13 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
 
   const int qr0 = qb0 + wave * 16; // this wave's first q row
   const int qrow = qr0 + fr;       // this lane's q row
+  // DOC: this row's band width (itself and the keys back to its document's
+  // first), the wave's smallest left bound and the block's first tile
+  int W_row = 0, lo_w = 0, t_doc = 0;
+  if constexpr (DOC) {
+    const DocBand db = doc_band(LO + (long)b_ * S, qrow, qb0, S);
+    W_row = db.w; lo_w = db.lo_w; t_doc = db.lo_b / KB;
+  }
 
   // Q fragments (B operand of S^T), PRE-SCALED by scale*log2(e): the
   // softmax runs in exp2 domain (v_exp2 without the fused multiply) and
@@ -329,7 +405,7 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
   const int kv_end = causal ? min(S, qb0 + QBLK) : S;
   const int n_tiles = (kv_end + KB - 1) / KB;
   // first tile: the one that holds the first key of the block's first row
-  const int t_beg = WIN ? max(0, qb0 - W + 1) / KB : 0;
+  const int t_beg = WIN ? max(0, qb0 - W + 1) / KB : (DOC ? t_doc : 0);
   constexpr int PF = TILE_K / (NTHR * 8);    // 16B vectors per thread
   stage_t<TR> kreg[PF], vreg[PF];
 
@@ -376,9 +452,11 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
     // a 128-row block spans 8 waves: tiles strictly above this wave's
     // causal diagonal are all-masked — skip the compute (NOT the
     // barriers: every wave still arrives at __syncthreads); under WIN
-    // so are tiles wholly left of the window of the wave's first row
+    // so are tiles wholly left of the window of the wave's first row,
+    // under DOC those wholly left of its document
     const bool wave_active = !(causal && kv0 > qr0 + 15) &&
-                             !(WIN && kv0 + KB - 1 <= qr0 - W);
+                             !(WIN && kv0 + KB - 1 <= qr0 - W) &&
+                             !(DOC && kv0 + KB - 1 < lo_w);
     if (wave_active) {
       // ---- S^T = K Q^T: lane col = qrow, regs = 16 keys ---------------
       f32x4 s_acc[KB / 16];
@@ -398,9 +476,11 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
       // ---- online softmax ---------------------------------------------
       // interior tiles (fully below the causal diagonal, fully in-range)
       // skip the per-element mask compares — most tiles at long S; under
-      // WIN a tile that the left edge of this row's window cuts has them
+      // WIN a tile that the left edge of this row's window cuts has them,
+      // under DOC one that holds keys before this row's document
       const bool need_mask = (causal && kv0 + KB - 1 > qrow)
-                             || (kv0 + KB > S) || (WIN && kv0 <= qrow - W);
+                             || (kv0 + KB > S) || (WIN && kv0 <= qrow - W)
+                             || (DOC && kv0 <= qrow - W_row);
       float mx = -1e30f;
       if (need_mask) {
         #pragma unroll
@@ -409,8 +489,9 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
           for (int r = 0; r < 4; ++r) {
             int kcol = kv0 + j * 16 + 4 * fg + r;
             float sv = s_acc[j][r];        // already scale*log2e scaled
-            if constexpr (WIN) {
-              if (!band_ok(kcol, qrow, W) || kcol >= S) sv = -1e30f;
+            if constexpr (WIN || DOC) {
+              if (!band_ok(kcol, qrow, DOC ? W_row : W) || kcol >= S)
+                sv = -1e30f;
             } else {
               if ((causal && kcol > qrow) || kcol >= S) sv = -1e30f;
             }
@@ -436,8 +517,10 @@ flash_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
       // o_acc stay 0, and alpha = exp2(0) = 1 scales zeros.  At the row's
       // first real tile alpha = exp2(-1e30 - m_new) = 0 as for any first
       // tile.  Every q row < S sees key i in some tile, so 1 / l_run needs
-      // no special case.
-      const float m_ref = (WIN && m_new == -1e30f) ? 0.f : m_new;
+      // no special case.  DOC is the same band with a left edge per row: a
+      // document that starts inside a wave's rows leaves the rows after it
+      // with leading tiles masked whole.
+      const float m_ref = ((WIN || DOC) && m_new == -1e30f) ? 0.f : m_new;
       float psum = 0.f;
       #pragma unroll
       for (int j = 0; j < KB / 16; ++j)
@@ -614,14 +697,48 @@ static fwd_kern_t ed_fwd_pick_win(bool ragged, bool gqa) {
                 : flash_fwd_kernel<D, true, false, false, true>;
 }
 
+// The document bounds of one launch: both or neither, int32 contiguous
+// [B, S] on q's device, causal and no window.  Their values are never read
+// here.  Returns whether they are given.
+static inline bool ed_attn_doc(const std::optional<at::Tensor>& lo,
+                               const std::optional<at::Tensor>& hi,
+                               const at::Tensor& q, bool causal,
+                               const std::optional<int64_t>& window,
+                               const char* who) {
+  TORCH_CHECK(lo.has_value() == hi.has_value(), who,
+              ": doc_lo and doc_hi come together");
+  if (!lo.has_value()) return false;
+  TORCH_CHECK(causal, who, ": document bounds need causal attention");
+  TORCH_CHECK(!window.has_value(), who,
+              ": document bounds and a window do not combine");
+  for (const at::Tensor* t : {&*lo, &*hi})
+    TORCH_CHECK(t->dtype() == at::kInt && t->is_contiguous() &&
+                t->dim() == 2 && t->size(0) == q.size(0) &&
+                t->size(1) == q.size(2) && t->device() == q.device(), who,
+                ": doc_lo and doc_hi must be contiguous int32 [B, S] on q's "
+                "device");
+  return true;
+}
+
+// The document instantiations: default forms, RAGGED = true for every S
+template <int D>
+static fwd_kern_t ed_fwd_pick_doc(bool gqa) {
+  return gqa ? flash_fwd_kernel<D, true, true, true, false, true>
+             : flash_fwd_kernel<D, true, true, false, false, true>;
+}
+
 std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(
     const at::Tensor& q_, const at::Tensor& k_, const at::Tensor& v_,
-    bool causal, std::optional<int64_t> window) {
+    bool causal, std::optional<int64_t> window,
+    const std::optional<at::Tensor>& doc_lo,
+    const std::optional<at::Tensor>& doc_hi) {
   auto q = ed_attn_arg(q_), k = ed_attn_arg(k_), v = ed_attn_arg(v_);
   const int G = ed_attn_group(q, k, v, "flash_attn_fwd");
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "flash_attn_fwd: D in {64,128}");
   TORCH_CHECK(S >= 1, "flash_attn_fwd: S >= 1");
+  const bool doc = ed_attn_doc(doc_lo, doc_hi, q, causal, window,
+                               "flash_attn_fwd");
   const bool ragged = S % (2 * QB) != 0;
   const int W = ed_attn_window(window, causal, S, "flash_attn_fwd");
   auto out = at::empty({B, H, S, D}, q.options());
@@ -632,8 +749,8 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(
   const int map_mode = ed_attn_map_mode();
   // LDS bytes -> workgroups per 160-KiB CU, D = 64 / 128:
   //   TR = 0: 48 / 80 KiB -> 3 / 2;  TR = 1: 32 / 64 KiB -> 5 / 2
-  const bool tr = (ragged || G > 1 || W) ? ATTN_TR_FWD
-                                         : ed_attn_tr(ATTN_TR_FWD);
+  const bool tr = (ragged || G > 1 || W || doc) ? ATTN_TR_FWD
+                                                : ed_attn_tr(ATTN_TR_FWD);
   static_assert(ATTN_TR_FWD == 1 && ATTN_TR_DQ == 1,
                 "the ragged and GQA fwd and dq kernels are instantiated "
                 "for TR = 1");
@@ -657,13 +774,17 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(
   if (W)
     kern = (D == 64) ? ed_fwd_pick_win<64>(ragged, G > 1)
                      : ed_fwd_pick_win<128>(ragged, G > 1);
+  if (doc)
+    kern = (D == 64) ? ed_fwd_pick_doc<64>(G > 1) : ed_fwd_pick_doc<128>(G > 1);
   hipLaunchKernelGGL(kern, grid, block, lds, stream,
       (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
       (const bf16*)v.data_ptr(), (bf16*)out.data_ptr(),
       lse.data_ptr<float>(), B, H, S, causal, scale,
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), map_mode, G, W);
+      v.stride(0), v.stride(1), v.stride(2), map_mode, G, W,
+      doc ? doc_lo->data_ptr<int>() : (const int*)nullptr,
+      doc ? doc_hi->data_ptr<int>() : (const int*)nullptr);
   return {out, lse};
 }
 
@@ -681,7 +802,7 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(
 // ---------------------------------------------------------------------------
 
 template <int D, bool TR, bool RAGGED = false, bool GQA = false,
-          bool WIN = false>
+          bool WIN = false, bool DOC = false>
 __global__ void __launch_bounds__(512)
 flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -691,8 +812,11 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                     long dsb, long dsh, long dss, long qsb, long qsh,
                     long qss, long ksb, long ksh, long kss, long vsb,
                     long vsh, long vss, long osb, long osh, long oss,
-                    int map_mode, int G, int W) {
+                    int map_mode, int G, int W,
+                    const int* __restrict__ LO, const int* __restrict__ HI) {
   static_assert(!WIN || TR, "the window kernels are instantiated for TR = 1");
+  static_assert(!DOC || (TR && RAGGED && !WIN),
+                "the document kernels are TR = 1, RAGGED, and not WIN");
   // 8 waves x 16 q rows: two 64-row halves share each staged K/V tile
   // (2x arithmetic intensity vs the 4-wave form) at 6+ waves/SIMD.
   // grid: 1-D, ceil(S/128) * B*H workgroups placed by attn_block_map
@@ -747,6 +871,12 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   const int qrow = qr0 + fr;
   const float lse_r = lse[rag_row<RAGGED>(qrow, S)];
   const float dlt_r = delta[rag_row<RAGGED>(qrow, S)];
+  // DOC: as in the forward
+  int W_row = 0, lo_w = 0, t_doc = 0;
+  if constexpr (DOC) {
+    const DocBand db = doc_band(LO + (long)b_ * S, qrow, qb0, S);
+    W_row = db.w; lo_w = db.lo_w; t_doc = db.lo_b / KB;
+  }
 
   f32x4 dq_acc[D / 16];
   #pragma unroll
@@ -786,7 +916,7 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     }
   };
   // WIN: first tile as in the forward, in the buffer of its parity
-  const int t_beg = WIN ? max(0, qb0 - W + 1) / KB : 0;
+  const int t_beg = WIN ? max(0, qb0 - W + 1) / KB : (DOC ? t_doc : 0);
   kv_load(t_beg * KB);
   kv_store(t_beg & 1);
   __syncthreads();
@@ -796,8 +926,9 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     const int bofs = (tt & 1) * DQBUF;
     if (tt + 1 < n_kt) kv_load(kv0 + KB);
     // tiles right of the wave's causal diagonal or (WIN) wholly left of
-    // the window of its first row: barriers only
-    if ((causal && kv0 > qr0 + 15) || (WIN && kv0 + KB - 1 <= qr0 - W)) {
+    // the window of its first row or (DOC) of its document: barriers only
+    if ((causal && kv0 > qr0 + 15) || (WIN && kv0 + KB - 1 <= qr0 - W) ||
+        (DOC && kv0 + KB - 1 < lo_w)) {
       if (tt + 1 < n_kt) kv_store((tt + 1) & 1);
       __syncthreads();
       continue;
@@ -824,15 +955,17 @@ flash_bwd_dq_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     }
     // dS = P * (dP - delta) * scale, P = exp(S*scale - lse)
     const bool need_mask = (causal && kv0 + KB - 1 > qrow)
-                           || (kv0 + KB > S) || (WIN && kv0 <= qrow - W);
+                           || (kv0 + KB > S) || (WIN && kv0 <= qrow - W)
+                           || (DOC && kv0 <= qrow - W_row);
     #pragma unroll
     for (int j = 0; j < KB / 16; ++j)
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float p = 0.f;
         int kcol = kv0 + j * 16 + 4 * fg + r;
-        if constexpr (WIN) {
-          if (!need_mask || (band_ok(kcol, qrow, W) && kcol < S))
+        if constexpr (WIN || DOC) {
+          if (!need_mask ||
+              (band_ok(kcol, qrow, DOC ? W_row : W) && kcol < S))
             p = __expf(s_acc[j][r] * scale - lse_r);
         } else {
           if (!need_mask || (!(causal && kcol > qrow) && kcol < S))
@@ -893,7 +1026,7 @@ template <int D, int NW> constexpr int dkv_waves_per_simd() {
   return NW == 8 ? 2 : (D == 64 ? 3 : 2);
 }
 template <int D, int SW, bool TR, bool RAGGED = false, bool GQA = false,
-          int NW = 8, bool HT = false, bool WIN = false>
+          int NW = 8, bool HT = false, bool WIN = false, bool DOC = false>
 __global__ void __launch_bounds__(NW * WAVE, (dkv_waves_per_simd<D, NW>()))
 flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -904,8 +1037,11 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                      long dsb, long dsh, long dss, long qsb, long qsh,
                      long qss, long ksb, long ksh, long kss, long vsb,
                      long vsh, long vss, long osb, long osh, long oss,
-                     int map_mode, int G, int W) {
+                     int map_mode, int G, int W,
+                     const int* __restrict__ LO, const int* __restrict__ HI) {
   static_assert(!(WIN && SW), "the window runs the strip form only");
+  static_assert(!DOC || (RAGGED && !SW && !WIN),
+                "the document kernels are RAGGED, strip form, and not WIN");
   // NW waves x 16 key rows share each staged Q/dO tile (see dq note)
   // grid: 1-D as in dq; kv block 0 is the causal-heavy one here, so the
   // map keeps the index order (heavy_last_index = false)
@@ -944,7 +1080,7 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   // 4-wave WIN: the wave index as a scalar, so that kr0 and the wave's mask
   // tests live in SGPRs (the GQA window kernels spilled without it; the
   // 8-wave ones spill more with it)
-  const int wave = (WIN && NW == 4)
+  const int wave = ((WIN || DOC) && NW == 4)
       ? __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE)
       : threadIdx.x / WAVE;
   const int kr0 = kb0 + wave * 16;          // this wave's first key row
@@ -1021,7 +1157,19 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
   // buffer parity is that of tt, so it runs on across a head switch, and
   // the trip count is block-uniform: every wave reaches every barrier.
   // WIN: the block's last key kb0 + KBLK - 1 is seen by W rows from itself on
-  const int q_end = WIN ? min(S, kb0 + KBLK - 1 + W) : S;
+  // DOC: its last key is seen up to the end of that key's document; hi_w is
+  // the end of the document of the wave's first key, the smallest of the
+  // wave, and a tile that stays below it needs no document test
+  const int* lo_b = nullptr;
+  int q_doc = 0, hi_w = 0;
+  if constexpr (DOC) {
+    lo_b = LO + (long)b_ * S;
+    const int* hi_b = HI + (long)b_ * S;
+    const int jb = min(kb0 + KBLK - 1, S - 1), jw = min(kr0, S - 1);
+    q_doc = min(max(hi_b[jb], jb + 1), S);
+    hi_w = min(max(hi_b[jw], jw + 1), S);
+  }
+  const int q_end = WIN ? min(S, kb0 + KBLK - 1 + W) : (DOC ? q_doc : S);
   const int n_qh = (q_end - q_start + QB - 1) / QB;   // tiles per query head
   const int n_qt = GQA ? G * n_qh : n_qh;
   int th = 0;
@@ -1063,7 +1211,8 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     // owns its columns 32 hh .. 32 hh + 31, so the halves never share an
     // element and no fence separates them.
     const bool need_mask = (causal && kr0 + 15 > q0) || (q0 + QB > S) ||
-                           (WIN && q0 + QB - 1 >= kr0 + W);
+                           (WIN && q0 + QB - 1 >= kr0 + W) ||
+                           (DOC && q0 + QB > hi_w);
     #pragma unroll
     for (int hh = 0; hh < QB / 32; ++hh) {
       f32x4 st_acc[2], dpt_acc[2];
@@ -1090,12 +1239,14 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
         const int j = 2 * hh + jj;
         int qcol = q0 + j * 16 + fr;
         float l = lse[rag_row<RAGGED>(qcol, S)];
+        int W_col = W;
+        if constexpr (DOC) W_col = doc_width(lo_b, qcol, S);
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           int krow = kr0 + 4 * fg + r;
           float p = 0.f;
-          if constexpr (WIN) {
-            if (!need_mask || (band_ok(krow, qcol, W) && qcol < S))
+          if constexpr (WIN || DOC) {
+            if (!need_mask || (band_ok(krow, qcol, W_col) && qcol < S))
               p = __expf(st_acc[jj][r] * scale - l);
           } else {
             if (!need_mask || (!(causal && krow > qcol) && qcol < S))
@@ -1181,7 +1332,8 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     // P^T = exp(S^T*scale - lse[qcol]); dS^T = P^T (dP^T - delta[qcol]) scale
     bf16x8v ptf[QB / 32];
     const bool need_mask = (causal && kr0 + 15 > q0) || (q0 + QB > S) ||
-                           (WIN && q0 + QB - 1 >= kr0 + W);
+                           (WIN && q0 + QB - 1 >= kr0 + W) ||
+                           (DOC && q0 + QB > hi_w);
     if (SW) {
       const int krow = kr0 + fr;             // this lane's key row
       // the 4 lse values a lane needs per j are CONSECUTIVE (4*fg+r):
@@ -1214,12 +1366,14 @@ flash_bwd_dkv_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
       for (int j = 0; j < QB / 16; ++j) {
         int qcol = q0 + j * 16 + fr;
         float l = lse[rag_row<RAGGED>(qcol, S)];
+        int W_col = W;
+        if constexpr (DOC) W_col = doc_width(lo_b, qcol, S);
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           int krow = kr0 + 4 * fg + r;
           float p = 0.f;
-          if constexpr (WIN) {
-            if (band_ok(krow, qcol, W) && qcol < S)
+          if constexpr (WIN || DOC) {
+            if (band_ok(krow, qcol, W_col) && qcol < S)
               p = __expf(st_acc[j][r] * scale - l);
           } else {
             if (!(causal && krow > qcol) && qcol < S)
@@ -1343,20 +1497,32 @@ static dq_kern_t ed_dq_pick_win(bool ragged, bool gqa) {
   return ragged ? flash_bwd_dq_kernel<D, true, true, false, true>
                 : flash_bwd_dq_kernel<D, true, false, false, true>;
 }
+// and the document ones, as ed_fwd_pick_doc
+template <int D>
+static dq_kern_t ed_dq_pick_doc(bool gqa) {
+  return gqa ? flash_bwd_dq_kernel<D, true, true, true, false, true>
+             : flash_bwd_dq_kernel<D, true, true, false, false, true>;
+}
 
 // The dkv instantiation and its LDS bytes for one launch.  sw and tr are
-// the A/B knobs and apply to the aligned MHA shapes only; ragged S, GQA and
-// a window run the strip form in the geometry's default TR.  The half-tile loop is
-// the 4-wave geometry's strip form.
+// the A/B knobs and apply to the aligned MHA shapes only; ragged S, GQA, a
+// window and document bounds run the strip form in the geometry's default
+// TR.  The half-tile loop is the 4-wave geometry's strip form.
 using dkv_kern_t = decltype(&flash_bwd_dkv_kernel<64, 0, false>);
 struct DkvLaunch { dkv_kern_t kern; size_t lds; };
 template <int D, int NW>
 static DkvLaunch ed_dkv_pick(bool sw, bool tr, bool ragged, bool gqa,
-                             bool win) {
+                             bool win, bool doc) {
   constexpr bool HT = NW == 4;
   constexpr bool TRD = ATTN_TR_DKV(D, NW);
   constexpr size_t L0 = sizeof(bf16) * dkv_lds_elems<D, false, NW>();
   constexpr size_t L1 = sizeof(bf16) * dkv_lds_elems<D, true, NW>();
+  if (doc)      // RAGGED = true for every S
+    return {gqa ? flash_bwd_dkv_kernel<D, 0, TRD, true, true, NW, HT, false,
+                                       true>
+                : flash_bwd_dkv_kernel<D, 0, TRD, true, false, NW, HT, false,
+                                       true>,
+            TRD ? L1 : L0};
   if (win) {
     if (gqa)
       return {ragged
@@ -1418,6 +1584,8 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
                       const at::Tensor& k_, const at::Tensor& v_,
                       const at::Tensor& out, const at::Tensor& lse,
                       bool causal, std::optional<int64_t> window,
+                      const std::optional<at::Tensor>& doc_lo,
+                      const std::optional<at::Tensor>& doc_hi,
                       bf16* dq_p, bf16* dk_p, bf16* dv_p,
                       long osb, long kosb, long osh, long oss) {
   // osb: batch stride of dq ([.., H, ..]); kosb: that of dk and dv
@@ -1435,6 +1603,10 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   TORCH_CHECK(S >= 1, "flash_attn_bwd: S >= 1");
   const bool ragged = S % (2 * QB) != 0;
   const int W = ed_attn_window(window, causal, S, "flash_attn_bwd");
+  const bool doc = ed_attn_doc(doc_lo, doc_hi, q, causal, window,
+                               "flash_attn_bwd");
+  const int* lo_p = doc ? doc_lo->data_ptr<int>() : nullptr;
+  const int* hi_p = doc ? doc_hi->data_ptr<int>() : nullptr;
   // delta = rowsum(dO * O), fp32 — one fused bf16 pass
   auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   {
@@ -1458,7 +1630,7 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   //   dkv (Q+dO+Q^T+dO^T, or Q+dO under TR), double-buffered, + strips:
   //     8 waves: TR = 0: 80 / 144 KiB -> 2 / 1;  TR = 1: 48 / 80 KiB -> 3 / 2
   //     4 waves: TR = 0: 72 / 136 KiB -> 2 / 1;  TR = 1: 40 / 72 KiB -> 4 / 2
-  const bool dflt = ragged || G > 1 || W;   // default forms only
+  const bool dflt = ragged || G > 1 || W || doc;   // default forms only
   const bool tr_q = dflt ? ATTN_TR_DQ : ed_attn_tr(ATTN_TR_DQ);
   size_t lds = sizeof(bf16) *
       (D == 64 ? (tr_q ? dq_lds_elems<64, true>() : dq_lds_elems<64, false>())
@@ -1481,6 +1653,8 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   if (W)
     qkern = (D == 64) ? ed_dq_pick_win<64>(ragged, G > 1)
                       : ed_dq_pick_win<128>(ragged, G > 1);
+  if (doc)
+    qkern = (D == 64) ? ed_dq_pick_doc<64>(G > 1) : ed_dq_pick_doc<128>(G > 1);
   // dkv: one workgroup of nw waves per block of nw * 16 keys of a K/V head
   // (the same grid as dq when nw == 8 and Hkv == H)
   static int swkv = []() {  // dkv butterfly measured SLOWER than the
@@ -1491,10 +1665,10 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
   const bool tr_d = nw == 4 ? ATTN_TR_DKV(D, 4) : ATTN_TR_DKV(D, 8);
   const bool tr_kv = dflt ? tr_d : ed_attn_tr(tr_d);
   const DkvLaunch kv = (D == 64)
-      ? (nw == 4 ? ed_dkv_pick<64, 4>(swkv, tr_kv, ragged, G > 1, W)
-                 : ed_dkv_pick<64, 8>(swkv, tr_kv, ragged, G > 1, W))
-      : (nw == 4 ? ed_dkv_pick<128, 4>(swkv, tr_kv, ragged, G > 1, W)
-                 : ed_dkv_pick<128, 8>(swkv, tr_kv, ragged, G > 1, W));
+      ? (nw == 4 ? ed_dkv_pick<64, 4>(swkv, tr_kv, ragged, G > 1, W, doc)
+                 : ed_dkv_pick<64, 8>(swkv, tr_kv, ragged, G > 1, W, doc))
+      : (nw == 4 ? ed_dkv_pick<128, 4>(swkv, tr_kv, ragged, G > 1, W, doc)
+                 : ed_dkv_pick<128, 8>(swkv, tr_kv, ragged, G > 1, W, doc));
   dim3 grid_kv = ed_attn_grid((S + nw * 16 - 1) / (nw * 16),
                               (long)B * (H / G), "flash_attn_bwd");
   dim3 block_kv(nw * WAVE);
@@ -1506,7 +1680,8 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       grad.stride(0), grad.stride(1), grad.stride(2),
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode, G, W);
+      v.stride(0), v.stride(1), v.stride(2), osb, osh, oss, map_mode, G, W,
+      lo_p, hi_p);
   hipLaunchKernelGGL(kv.kern, grid_kv, block_kv, kv.lds, stream,
       (const bf16*)grad.data_ptr(), (const bf16*)q.data_ptr(),
       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
@@ -1516,14 +1691,16 @@ flash_attn_bwd_launch(const at::Tensor& grad_, const at::Tensor& q_,
       q.stride(0), q.stride(1), q.stride(2),
       k.stride(0), k.stride(1), k.stride(2),
       v.stride(0), v.stride(1), v.stride(2), kosb, osh, oss, map_mode, G,
-      W);
+      W, lo_p, hi_p);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor>
 flash_attn_bwd(const at::Tensor& grad_, const at::Tensor& q_,
                const at::Tensor& k_, const at::Tensor& v_,
                const at::Tensor& out, const at::Tensor& lse, bool causal,
-               std::optional<int64_t> window) {
+               std::optional<int64_t> window,
+               const std::optional<at::Tensor>& doc_lo,
+               const std::optional<at::Tensor>& doc_hi) {
   const int B = q_.size(0), H = q_.size(1), S = q_.size(2), D = q_.size(3);
   auto opts = q_.options();
   auto dq = at::empty({B, H, S, D}, opts);
@@ -1532,7 +1709,7 @@ flash_attn_bwd(const at::Tensor& grad_, const at::Tensor& q_,
   auto dk = at::empty({B, Hkv, S, D}, opts);
   auto dv = at::empty({B, Hkv, S, D}, opts);
   flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal, window,
-                        (bf16*)dq.data_ptr(), (bf16*)dk.data_ptr(),
+                        doc_lo, doc_hi, (bf16*)dq.data_ptr(), (bf16*)dk.data_ptr(),
                         (bf16*)dv.data_ptr(),
                         (long)H * S * D, (long)Hkv * S * D, (long)S * D, D);
   return {dq, dk, dv};
@@ -1558,7 +1735,7 @@ flash_attn_bwd_pack(const at::Tensor& grad_, const at::Tensor& q_,
   // dq/dk/dv sections at column offsets 0, H*D, (H+Hkv)*D of the packed
   // rows; per-(b,h,s,d) element strides: osb=S*W, osh=D, oss=W
   flash_attn_bwd_launch(grad_, q_, k_, v_, out, lse, causal, std::nullopt,
-                        base, base + H * D, base + (H + Hkv) * D,
+                        std::nullopt, std::nullopt, base, base + H * D, base + (H + Hkv) * D,
                         S * W, S * W, D, W);
   return dqkv;
 }

@@ -58,12 +58,16 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q,
                                                   const at::Tensor& k,
                                                   const at::Tensor& v,
                                                   bool causal,
-                                                  std::optional<int64_t> window);
+                                                  std::optional<int64_t> window,
+                                                  const std::optional<at::Tensor>& doc_lo,
+                                                  const std::optional<at::Tensor>& doc_hi);
 std::tuple<at::Tensor, at::Tensor, at::Tensor>
 flash_attn_bwd(const at::Tensor& grad, const at::Tensor& q,
                const at::Tensor& k, const at::Tensor& v,
                const at::Tensor& out, const at::Tensor& lse, bool causal,
-               std::optional<int64_t> window);
+               std::optional<int64_t> window,
+               const std::optional<at::Tensor>& doc_lo,
+               const std::optional<at::Tensor>& doc_hi);
 at::Tensor
 flash_attn_bwd_pack(const at::Tensor& grad, const at::Tensor& q,
                     const at::Tensor& k, const at::Tensor& v,
@@ -176,11 +180,15 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
   m.def("gelu_fast(Tensor x) -> Tensor");
   m.def("gelu_bwd_fast(Tensor g, Tensor x) -> Tensor");
   // window: sliding-window causal attention, row i sees keys i - window + 1
-  // .. i; unset, the four- and seven-argument calls are what they were
+  // .. i; unset, the four- and seven-argument calls are what they were.
+  // doc_lo, doc_hi: int32 [B, S] document bounds of packed sequences, row i
+  // sees keys doc_lo[b, i] .. i; unset, every shorter call is what it was
   m.def("flash_attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, "
-        "int? window=None) -> (Tensor, Tensor)");
+        "int? window=None, Tensor? doc_lo=None, Tensor? doc_hi=None) "
+        "-> (Tensor, Tensor)");
   m.def("flash_attn_bwd(Tensor grad, Tensor q, Tensor k, Tensor v, "
-        "Tensor out, Tensor lse, bool causal, int? window=None) "
+        "Tensor out, Tensor lse, bool causal, int? window=None, "
+        "Tensor? doc_lo=None, Tensor? doc_hi=None) "
         "-> (Tensor, Tensor, Tensor)");
   m.def("flash_attn_bwd_pack(Tensor grad, Tensor q, Tensor k, Tensor v, "
         "Tensor out, Tensor lse, bool causal) -> Tensor");
