@@ -2,7 +2,11 @@
 """GEMM microbenchmark: hand-written MFMA kernels vs hipBLASLt (aten).
 
 Times every linear-layer shape of the GPT-2-small b64/s1024 bench step
-(fwd NT, dX NT-with-weight-transpose, dW TN) plus square probes.
+(fwd NT, dX NT-with-weight-transpose, dX NN, dW TN) plus square probes.
+The NN rows time three routes of dX = dY @ W on the weight as it lies: the
+native gemm_nn kernel, the older hand route (transposed weight copy +
+gemm_nt, copy included) and aten's strided mm; --nn-only times just those,
+the routes alternating inside each repeat.
 Prints TFLOP/s for both paths; this is the evidence base for the
 per-shape dispatch policy (ops/gemm.py).
 
@@ -68,6 +72,28 @@ def bench_tn(ext, R, P, Q):
     return {"shape": f"TN r{R} {P}x{Q}",
             "hand_tf": fl / t_hand / 1e9, "aten_tf": fl / t_aten / 1e9,
             "hand_ms": t_hand, "aten_ms": t_aten, "max_err_vs_blaslt": err}
+
+
+def bench_nn(ext, M, N, K, repeats=5, iters=20):
+    """dX = a @ b, b [K, N] row-major: native NN kernel, the transposed-copy
+    route, aten's strided mm; medians over repeats, routes alternating."""
+    a = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+    b = torch.randn(K, N, device="cuda", dtype=torch.bfloat16)
+    routes = {"nn": lambda: ext.gemm_nn(a, b, None),
+              "copy_nt": lambda: ext.gemm_nt(a, b.t().contiguous(), None),
+              "aten": lambda: torch.mm(a, b)}
+    t = {k: [] for k in routes}
+    for _ in range(repeats):
+        for k, fn in routes.items():
+            t[k].append(time_ms(fn, iters))
+    fl = 2.0 * M * N * K
+    err = float((routes["nn"]().float() - routes["aten"]().float())
+                .abs().max())
+    r = {"shape": f"NN {M}x{N}x{K}", "max_err_vs_blaslt": err}
+    for k in routes:
+        r[k + "_ms"] = stats(t[k])
+        r[k + "_tf"] = fl / r[k + "_ms"]["med"] / 1e9
+    return r
 
 
 def stats(xs):
@@ -149,7 +175,8 @@ def main():
     p.add_argument("--hidden", type=int, default=768)
     p.add_argument("--vocab", type=int, default=50304)
     p.add_argument("--only", default=None,
-                   help="single shape 'nt,M,N,K' or 'tn,R,P,Q' (for PMC runs)")
+                   help="single shape 'nt,M,N,K', 'nn,M,N,K' or 'tn,R,P,Q' (for PMC "
+                        "runs)")
     p.add_argument("--tn-map", choices=["0", "1", "both"], default=None,
                    help="with --only tn,...: time gemm_tn under workgroup "
                         "map 0 (tile-major), 1 (slice-major) or both, "
@@ -161,6 +188,8 @@ def main():
                    help="with --tn-map: comma-separated r-loop staging "
                         "variants of the 256-tile kernel to sweep (1 = "
                         "three-buffer ring, 0 = issue-then-drain)")
+    p.add_argument("--nn-only", action="store_true",
+                   help="only the NN (dX) rows, at --hidden's dX shapes")
     p.add_argument("--repeats", type=int, default=5)
     p.add_argument("--iters", type=int, default=30)
     p.add_argument("--warm-iters", type=int, default=50)
@@ -186,9 +215,24 @@ def main():
             return
         if parts[0] == "nt":
             r = bench_nt(ext, int(parts[1]), int(parts[2]), int(parts[3]))
+        elif parts[0] == "nn":
+            r = bench_nn(ext, int(parts[1]), int(parts[2]), int(parts[3]),
+                         args.repeats)
         else:
             r = bench_tn(ext, int(parts[1]), int(parts[2]), int(parts[3]))
         print(json.dumps(r))
+        return
+    # dX shapes (N, K), as the NT list below has them
+    dx_shapes = [(H, 3 * H), (H, H), (H, 4 * H), (4 * H, H), (H, V)]
+    nn_rows = [bench_nn(ext, M, N, K, args.repeats) for (N, K) in dx_shapes]
+    for r in nn_rows:
+        print(f"{r['shape']:>28}: " + "  ".join(
+            f"{k} {r[k + '_tf']:6.1f} TF ({r[k + '_ms']['med']:7.3f} ms, "
+            f"{r[k + '_ms']['min']:.3f}-{r[k + '_ms']['max']:.3f})"
+            for k in ("nn", "copy_nt", "aten"))
+            + f"  err {r['max_err_vs_blaslt']:.3f}", flush=True)
+    if args.nn_only:
+        print(json.dumps(nn_rows))
         return
     rows = []
     # square probes (vs guide ladder numbers)
@@ -199,7 +243,7 @@ def main():
                       (H, 4 * H, True), (V, H, False)]:
         rows.append(bench_nt(ext, M, N, K, bias=b))
     # dX (NT with transposed weight)
-    for (N, K) in [(H, 3 * H), (H, H), (H, 4 * H), (4 * H, H), (H, V)]:
+    for (N, K) in dx_shapes:
         rows.append(bench_nt(ext, M, N, K))
     # dW (TN)
     for (P, Q) in [(3 * H, H), (H, H), (4 * H, H), (H, 4 * H), (V, H)]:
@@ -209,7 +253,7 @@ def main():
         print(f"{r['shape']:>28}: hand {r['hand_tf']:7.1f} TF "
               f"({r['hand_ms']:7.3f} ms)  aten {r['aten_tf']:7.1f} TF "
               f"({r['aten_ms']:7.3f} ms)  err {r['max_err_vs_blaslt']:.3f}")
-    print(json.dumps(rows))
+    print(json.dumps(rows + nn_rows))
 
 
 if __name__ == "__main__":

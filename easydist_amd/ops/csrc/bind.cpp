@@ -52,6 +52,11 @@ std::tuple<at::Tensor, at::Tensor> gemm_tn_asum(const at::Tensor& a,
 std::tuple<at::Tensor, at::Tensor>
 gemm_nt_gelu(const at::Tensor& a, const at::Tensor& bt,
              const std::optional<at::Tensor>& bias, bool tanh_approx);
+at::Tensor gemm_nn(const at::Tensor& a, const at::Tensor& b,
+                   const std::optional<at::Tensor>& bias);
+at::Tensor gemm_nn_act(const at::Tensor& a, const at::Tensor& b,
+                       const std::optional<at::Tensor>& bias, int64_t act,
+                       const std::optional<at::Tensor>& aux);
 at::Tensor gelu_fast(const at::Tensor& x);
 at::Tensor gelu_bwd_fast(const at::Tensor& g, const at::Tensor& x);
 std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q,
@@ -177,6 +182,9 @@ TORCH_LIBRARY(easydist_amd_hip, m) {
   m.def("gemm_tn_asum(Tensor a, Tensor b) -> (Tensor, Tensor)");
   m.def("gemm_nt_gelu(Tensor a, Tensor bt, Tensor? bias, bool tanh_approx) "
         "-> (Tensor, Tensor)");
+  m.def("gemm_nn(Tensor a, Tensor b, Tensor? bias) -> Tensor");
+  m.def("gemm_nn_act(Tensor a, Tensor b, Tensor? bias, int act, "
+        "Tensor? aux) -> Tensor");
   m.def("gelu_fast(Tensor x) -> Tensor");
   m.def("gelu_bwd_fast(Tensor g, Tensor x) -> Tensor");
   // window: sliding-window causal attention, row i sees keys i - window + 1
@@ -232,6 +240,8 @@ TORCH_LIBRARY_IMPL(easydist_amd_hip, CUDA, m) {
   m.impl("gemm_nt_act", gemm_nt_act);
   m.impl("gemm_tn_asum", gemm_tn_asum);
   m.impl("gemm_nt_gelu", gemm_nt_gelu);
+  m.impl("gemm_nn", gemm_nn);
+  m.impl("gemm_nn_act", gemm_nn_act);
   m.impl("gelu_fast", gelu_fast);
   m.impl("gelu_bwd_fast", gelu_bwd_fast);
   m.impl("flash_attn_fwd", flash_attn_fwd);

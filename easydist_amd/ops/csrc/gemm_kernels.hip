@@ -1,13 +1,13 @@
 // Hand-written MFMA bf16 GEMM family for gfx950.
 //
-// Three kernel families cover the linear-layer training shapes the
-// compiler's lowering pass (compiler/passes/lower_hip.py) emits, and a
-// fourth, moe_nn (grouped NN, optional fused SwiGLU; described at its
-// definition), the MoE expert FFN forward:
+// Three dense layouts cover the linear-layer training shapes the
+// compiler's lowering pass (compiler/passes/lower_hip.py) emits -- NT the
+// forward, NN the dX backward, TN the dW backward -- and the grouped moe_nn /
+// moe_nt / moe_tn kernels (described at their definitions) the MoE expert
+// FFN:
 //
-//   gemm_nt_256  C[M,N] = A[M,K] @ Bt[N,K]^T (+bias)  -- fwd linears and,
-//       with a (cheap, weight-only) transpose in the graph, the dX
-//       backward.  256x256x64 tile, 8 waves, 8-phase software-pipelined
+//   gemm_nt_256  C[M,N] = A[M,K] @ Bt[N,K]^T (+bias)  -- fwd linears.
+//       256x256x64 tile, 8 waves, 8-phase software-pipelined
 //       schedule (cdna_hip_programming.md "256-sq 8-phase template"):
 //       global_load_lds staging with the st_16x32 XOR swizzle applied on
 //       the SOURCE address, counted s_waitcnt vmcnt(6) once per K-tile,
@@ -17,6 +17,13 @@
 //   gemm_nt_128  same contract, 128x128x32 tile (the ladder step-3
 //       structure) for edge/small shapes; row-clamped staging so M,N need
 //       not be tile multiples.
+//   gemm_nn_256  C[M,N] = A[M,K] @ B[K,N] (+bias)  -- the dX backward
+//       (dX = dY @ W) on the weight as it lies: gemm_nt_256's tile, A half
+//       and schedule, with B staged k-major (coalesced: global rows ARE
+//       k-rows) into two 32-row tr-read images per tile and read with
+//       ds_read_b64_tr_b16.  No transposed copy of B, in HBM or in LDS.
+//   gemm_nn_128  same contract for edge/small shapes: moe_nn's plain body
+//       with one expert, plus the bias.
 //   gemm_tn      C[P,Q] = sum_r A[r,P] * B[r,Q]  -- the dW backward
 //       (both operands reduce-dim-strided activations; transposing them
 //       globally would cost ~the GEMM itself).  Tiles stage k-major
@@ -280,6 +287,107 @@ gemm_nt_128(const bf16* __restrict__ A, const bf16* __restrict__ Bt,
 // {16g..16g+15}.  The 1-bit st_16x32 form and a 2-bit form for strided
 // groups were A/B'd on hardware and lost.
 DEVINL unsigned sw32(unsigned x) { return x ^ (((x >> 8) & 7u) << 4); }
+
+// gemm_nt_256's A half (staging, fragment reads) and epilogue as functions,
+// for gemm_nn_256, which takes the same A [M,K] and ends with the same
+// accumulator layout.  gemm_nt_256 keeps its own inline copies: built on
+// these functions its ISA changed and it measured 1.5-2% slower at two of
+// five shapes (profiles/README.md Round 17).
+//
+// One A half = 16 KiB = 2 glds/thread to smem + dst0.  The LDS image is
+// lane-linear; the inverse st_16x32 swizzle is applied to the per-lane
+// SOURCE address, source rows clamped to M-1.
+DEVINL void g256_stage_a(const bf16* __restrict__ A, int M, int K, unsigned m0,
+                         int k0, int h, char* smem, unsigned dst0, int t,
+                         int wave) {
+  #pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    unsigned p = (i * 512 + t) * 16;          // linear byte pos in half
+    unsigned L = sw32(p);                     // logical (image) byte
+    int s = L >> 13;                          // stripe (8 KiB each)
+    int row = (L >> 7) & 63;
+    int k = (L & 127) >> 1;
+    int grow = min((int)m0 + s * 128 + h * 64 + row, M - 1);
+    glds16(A + (long)grow * K + k0 + k,
+           smem + dst0 + (i * 512 + wave * 64) * 16);
+  }
+}
+
+// wave row wr's 64 rows x 64 k of the A half at smem + base as MFMA fragments
+// (swizzled ds_read_b128)
+DEVINL void g256_read_a(bf16x8v (&a)[4][2], const char* smem, unsigned base,
+                        int wr, int fr, int fg) {
+  #pragma unroll
+  for (int i = 0; i < 4; ++i)
+    #pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      unsigned L = wr * 8192u + (i * 16 + fr) * 128u + (kk * 32 + fg * 8) * 2u;
+      a[i][kk] = *reinterpret_cast<const bf16x8v*>(smem + base + sw32(L));
+    }
+}
+
+// LDS-bounced coalesced stores of a wave's 128x64 accumulators (rows
+// wr*128.., cols wc*64.. of the tile at (m0, n0); a lane holds col l&15,
+// rows (l>>4)*4+r of each 16x16 block), bias and activation applied.  The
+// caller has drained the LDS-DMA queue and passed a barrier.
+DEVINL void g256_epilogue(f32x4 (&acc)[8][4], char* smem,
+                          bf16* __restrict__ C, const bf16* __restrict__ bias,
+                          bf16* __restrict__ aux, int act, int M, int N,
+                          unsigned m0, unsigned n0, int wave, int lane) {
+  const int fr = lane & 15, fg = lane >> 4;
+  // Repurpose the wave's 16 KiB share as a [128][64] bf16 bounce so
+  // global stores are 16-B wide and row-contiguous.
+  bf16* share = reinterpret_cast<bf16*>(smem) + wave * 8192;
+  const unsigned wm = (wave >> 2) * 128, wn = (wave & 3) * 64;
+  // hoisted bias loads (4 per lane) -- see gemm_nt_128 epilogue note
+  float bias_v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (bias) {
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      bias_v[j] = bf2f(bias[min((int)(n0 + wn + j * 16 + fr), N - 1)]);
+  }
+  #pragma unroll
+  for (int i = 0; i < 8; ++i)
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int row = i * 16 + fg * 4 + r;
+        int col = j * 16 + fr;
+        share[row * 64 + col] = f2bf(acc[i][j][r] + bias_v[j]);
+      }
+  lds_fence();   // own-wave LDS writes -> reads; no cross-wave traffic
+  #pragma unroll
+  for (int tt = 0; tt < 16; ++tt) {
+    int row = tt * 8 + (lane >> 3);
+    int colc = (lane & 7) * 8;
+    int gm = m0 + wm + row;
+    int gn = n0 + wn + colc;
+    if (gm < (int)M && gn + 8 <= (int)N) {
+      bf16x8v val = *reinterpret_cast<const bf16x8v*>(&share[row * 64 + colc]);
+      if (act) {
+        bf16x8v av{};
+        if (act == 2 || act == 4)
+          av = *reinterpret_cast<const bf16x8v*>(&aux[(long)gm * N + gn]);
+        else if (act >= 5)   // fused fwd: keep pre-act for gelu_backward
+          *reinterpret_cast<bf16x8v*>(&aux[(long)gm * N + gn]) = val;
+        #pragma unroll
+        for (int e = 0; e < 8; ++e)
+          val[e] = (__bf16)act_apply(act, bf2f((bf16)val[e]),
+                                     bf2f((bf16)av[e]));
+      }
+      *reinterpret_cast<bf16x8v*>(&C[(long)gm * N + gn]) = val;
+    } else if (gm < (int)M) {
+      for (int e = 0; e < 8 && gn + e < (int)N; ++e) {
+        float xv = bf2f(share[row * 64 + colc + e]);
+        float axv = (act == 2 || act == 4)
+                        ? bf2f(aux[(long)gm * N + gn + e]) : 0.f;
+        if (act >= 5) aux[(long)gm * N + gn + e] = f2bf(xv);
+        C[(long)gm * N + gn + e] = f2bf(act_apply(act, xv, axv));
+      }
+    }
+  }
+}
 
 extern "C" __global__ void __launch_bounds__(512)
 gemm_nt_256(const bf16* __restrict__ A, const bf16* __restrict__ Bt,
@@ -725,6 +833,167 @@ TN_KERNEL(gemm_tn_256_kernel, TBP2, 1)
 TN_KERNEL(gemm_tn_256_drain_kernel, TBP2, 0)
 
 // ===========================================================================
+// gemm_nn_256: C[M,N] = A[M,K] @ B[K,N] (+bias[N]), act_apply epilogue -- the
+// dX backward (dX = dY @ W) on the weight as it lies in memory.  No
+// transposed copy of B exists anywhere, in HBM or in LDS.
+// Takes M >= 256, N >= 256, K % 64 == 0, N % 8 == 0; everything else in the
+// op's envelope goes to gemm_nn_128 (moe_nn_body).
+//
+// 256x256 output tile, 8 waves (wave (wr, wc): rows wr*128..+128, cols
+// wc*64..+64, acc[8][4]), 64 k per tile: gemm_nt_256's frame with a B side
+// of its own.
+//
+// LDS map (128 KiB, one extern __shared__ object), buf b (0/1) at b*65536:
+//   A half h at h*16384: gemm_nt_256's image (g256_stage_a / g256_read_a:
+//       glds with the swizzle on the source address, rows clamped to M-1)
+//   B image h at 32768 + h*16384: k-rows h*32..+32 of the tile, all 256
+//       columns, as tn_stage<512>'s tr-read image.  Global rows ARE k-rows,
+//       so the stage is coalesced along N; tn_stage's pmax - 8 clamp keeps
+//       the N edge tile's reads inside the row (duplicate columns, masked
+//       by the epilogue).  tn_frag (2 ds_read_b64_tr_b16) gives "n = l&15,
+//       k = 8*(l>>4)+0..7" -- the operand form the A fragment has for its
+//       rows, so image h pairs with the A fragments' kk = h.
+//
+// MFMA operand order: mfma(a_frag, b_frag), D[m][n] as in gemm_nt_256 (a lane
+// ends with col l&15, rows (l>>4)*4+r), NOT moe_nn's transposed product: the
+// epilogue is then gemm_nt_256's, as a function (g256_epilogue), and its
+// per-wave bounce needs no cross-wave barrier.
+//
+// Phase schedule per K-tile T.  gemm_nt_256 splits B by column halves and a
+// phase is a (row half, column half) quadrant; here B splits by k, so a
+// phase is (row half mh, k half kh): 4 i x 4 j x 1 kk = the same 16 MFMAs,
+// order (0,0),(0,1),(1,1),(1,0) so consecutive phases share one operand:
+//   q0: read A-h0 (8x ds_read_b128), B-img0 + B-img1 (16x tr_b64)
+//                                          stage B-img0(T+1)
+//   q1: [A-h0, B-img1 kept in registers]   stage A-h0(T+2)
+//   q2: read A-h1 (8)   [B-img1 kept]      stage B-img1(T+2)
+//   q3: [A-h1, B-img0 kept]                stage A-h1(T+2), vmcnt(6)
+// Every half is read in the same phase as its gemm_nt_256 counterpart and
+// every stage is 2 glds per thread, so that kernel's arguments carry over
+// unchanged: one closing raw barrier per phase, vmcnt(6) leaving the 3
+// newest halves in flight, 7 halves in the prologue, dummy stages (k0 = 0,
+// valid memory, never read) at the K tail so the count stays constant.
+// Never __syncthreads: its fence would drain the LDS-DMA in flight.
+//
+// Workgroup order: xcd_swizzle with the column tile fastest, as gemm_nt_256.
+// For dX, M is the token count and N the layer width: the N/256 (3 to 12)
+// consecutive workgroups of one XCD stream one A row panel from HBM once and
+// cycle through the few B column panels, each re-used every N/256-th
+// workgroup and L2-resident (the whole weight is a few MiB).
+//
+// The body is an inlined function under a thin kernel, as tn_body is: written
+// straight into the kernel, hipcc put an s_waitcnt vmcnt(0) in front of q0's
+// tr reads (it was in the ISA), which drains the stages in flight once per
+// tile.  Check the loop's ISA after touching this: one vmcnt(6), no vmcnt(0).
+// ===========================================================================
+DEVINL void nn256_body(const bf16* __restrict__ A, const bf16* __restrict__ B,
+                       bf16* __restrict__ C, const bf16* __restrict__ bias,
+                       bf16* __restrict__ aux, int act, int M, int N, int K) {
+  // aux: INPUT for bwd modes 2/4 (saved pre-act), OUTPUT for fwd 5/6
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  unsigned nwg_m = (M + BM2 - 1) / BM2, nwg_n = (N + BN2 - 1) / BN2;
+  unsigned wg = xcd_swizzle(blockIdx.x, nwg_m * nwg_n);
+  const unsigned m0 = (wg / nwg_n) * BM2;
+  const unsigned n0 = (wg % nwg_n) * BN2;
+
+  const int t = threadIdx.x;
+  const int lane = t % WAVE;
+  const int wave = t / WAVE;
+  const int wr = wave >> 2;           // wave row (0/1): rows wr*128..+128
+  const int wc = wave & 3;            // wave col (0..3): cols wc*64..+64
+  const int fr = lane & 15;
+  const int fg = lane >> 4;
+
+  auto stage_a = [&](int parity, int k0, int h) {
+    g256_stage_a(A, M, K, m0, k0, h, smem, parity * BUF_B + h * HALF_B, t,
+                 wave);
+  };
+  auto stage_b = [&](int parity, int k0, int h) {
+    tn_stage<512>(B, N, k0 + h * 32, (int)n0, N,
+                  smem + parity * BUF_B + 32768u + h * HALF_B, t, wave);
+  };
+  auto read_a = [&](bf16x8v (&a)[4][2], int tile, int mh) {
+    g256_read_a(a, smem, (tile & 1) * BUF_B + mh * HALF_B, wr, fr, fg);
+  };
+  // the wave's 4 column chunks of k image kh
+  auto read_b = [&](bf16x8v (&b)[4], int tile, int kh) {
+    const char* img = smem + (tile & 1) * BUF_B + 32768u + kh * HALF_B;
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = tn_frag(img, wc * 4 + j, lane);
+  };
+
+  f32x4 acc[8][4];
+  #pragma unroll
+  for (int i = 0; i < 8; ++i)
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+      acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  bf16x8v a_frag[4][2], b0_frag[4], b1_frag[4];
+  const int NT = K / BK2;
+
+  // k0 of tile t, clamped to a dummy (t >= NT: data never read)
+  auto k_of = [&](int t) { return t < NT ? t * BK2 : 0; };
+
+  // prologue: tile0 fully + A0,B1,A1 of tile1 (B0(1) staged in q0 of T=0);
+  // always 7 halves = 14 loads so vmcnt(6) drains exactly tile 0
+  stage_a(0, 0, 0); stage_a(0, 0, 1); stage_b(0, 0, 0); stage_b(0, 0, 1);
+  stage_a(1, k_of(1), 0); stage_b(1, k_of(1), 1); stage_a(1, k_of(1), 1);
+  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  raw_barrier();
+
+  auto mfma_phase = [&](int mh, int kh, bf16x8v (&bf)[4]) {
+    __builtin_amdgcn_s_setprio(1);
+    #pragma unroll
+    for (int i = 0; i < 4; ++i)
+      #pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[mh * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a_frag[i][kh], bf[j], acc[mh * 4 + i][j], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  for (int T = 0; T < NT; ++T) {
+    // q0: (mh0, k0); both B images read here (B-img1(T) was staged a full
+    // tile before B-img0(T)), so q1/q3 have no LDS reads at all
+    read_a(a_frag, T, 0);
+    read_b(b0_frag, T, 0);
+    read_b(b1_frag, T, 1);
+    stage_b((T + 1) & 1, k_of(T + 1), 0);
+    mfma_phase(0, 0, b0_frag);
+    raw_barrier();
+    // q1: (mh0, k1) -- A and B-img1 kept
+    stage_a(T & 1, k_of(T + 2), 0);
+    mfma_phase(0, 1, b1_frag);
+    raw_barrier();
+    // q2: (mh1, k1) -- B-img1 kept
+    read_a(a_frag, T, 1);
+    stage_b(T & 1, k_of(T + 2), 1);
+    mfma_phase(1, 1, b1_frag);
+    raw_barrier();
+    // q3: (mh1, k0) -- A kept, B-img0 kept from q0
+    stage_a(T & 1, k_of(T + 2), 1);
+    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    mfma_phase(1, 0, b0_frag);
+    raw_barrier();
+  }
+
+  // drain the dummy stages of the tail before the bounce reuses their LDS
+  // (see gemm_nt_256)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  raw_barrier();
+  g256_epilogue(acc, smem, C, bias, aux, act, M, N, m0, n0, wave, lane);
+}
+
+extern "C" __global__ void __launch_bounds__(512)
+gemm_nn_256(const bf16* __restrict__ A, const bf16* __restrict__ B,
+            bf16* __restrict__ C, const bf16* __restrict__ bias,
+            bf16* __restrict__ aux, int act, int M, int N, int K) {
+  nn256_body(A, B, C, bias, aux, act, M, N, K);
+}
+
+// ===========================================================================
 // moe_nn: the MoE expert FFN forward, one grouped NN GEMM template.
 //   plain :  C[e] = X[e] @ W[e]           X [E,R,K], W [E,K,N] -> C [E,R,N]
 //   swiglu:  A[e] = X[e] @ W1[e], B[e] = X[e] @ W3[e],
@@ -765,13 +1034,13 @@ TN_KERNEL(gemm_tn_256_drain_kernel, TBP2, 0)
 #define NN_BK 32
 using bf16x4v = __attribute__((ext_vector_type(4))) __bf16;
 
-template <bool SWIGLU>
+template <bool SWIGLU, bool BIAS = false>
 DEVINL void moe_nn_body(const bf16* __restrict__ X,
                         const bf16* __restrict__ W1,
                         const bf16* __restrict__ W3, bf16* __restrict__ Out,
                         bf16* __restrict__ Aout, bf16* __restrict__ Bout,
                         const unsigned char* __restrict__ valid, int R, int K,
-                        int N) {
+                        int N, const bf16* __restrict__ bias = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NP = SWIGLU ? 2 : 1;           // products per workgroup
   constexpr int TN = SWIGLU ? 64 : 128;        // output columns per product
@@ -932,6 +1201,23 @@ DEVINL void moe_nn_body(const bf16* __restrict__ X,
     __syncthreads();
     store_tile(Bout, from(smem));
   } else {
+    if constexpr (BIAS) {
+      // bias[N] (optional; the dense gemm_nn_128 only, the MoE entries are
+      // built without): added in fp32 to the lane's 4 columns, so the output
+      // is still rounded once
+      if (bias) {
+        #pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          f32x4 bv;
+          #pragma unroll
+          for (int r = 0; r < 4; ++r)
+            bv[r] = bf2f(
+                bias[min(n0 + wn + j * 16 + (lane >> 4) * 4 + r, N - 1)]);
+          #pragma unroll
+          for (int i = 0; i < 4; ++i) acc[0][i][j] += bv;
+        }
+      }
+    }
     #pragma unroll
     for (int i = 0; i < 4; ++i)
       #pragma unroll
@@ -957,6 +1243,17 @@ moe_nn_swiglu_kernel(const bf16* __restrict__ X, const bf16* __restrict__ W1,
                      const unsigned char* __restrict__ valid, int R, int K,
                      int N) {
   moe_nn_body<true>(X, W1, W3, H, A, B, valid, R, K, N);
+}
+
+// gemm_nn_128: the dense NN GEMM for the shapes gemm_nn_256 does not take
+// (M < 256, N < 256 or K % 64 != 0): moe_nn's plain form with one expert and
+// no valid flags -- any M, N % 8 == 0, K % 32 == 0 -- plus the bias.
+extern "C" __global__ void __launch_bounds__(256)
+gemm_nn_128(const bf16* __restrict__ A, const bf16* __restrict__ B,
+            bf16* __restrict__ C, const bf16* __restrict__ bias, int M, int N,
+            int K) {
+  moe_nn_body<false, true>(A, B, nullptr, C, nullptr, nullptr, nullptr, M, K,
+                           N, bias);
 }
 
 // ===========================================================================
@@ -1324,6 +1621,21 @@ moe_tn2_kernel(const bf16* __restrict__ X, const bf16* __restrict__ G1,
 // ===========================================================================
 // host wrappers
 // ===========================================================================
+// edge-shape paths (gemm_nt_128, gemm_nn_128): the activation as a separate
+// aten pass over the GEMM's (bias included) result
+static at::Tensor act_pass(at::Tensor c, int64_t act,
+                           const std::optional<at::Tensor>& aux) {
+  if (act == 1) c = at::gelu(c, "tanh");
+  else if (act == 3) c = at::gelu(c);
+  else if (act == 2) c = at::gelu_backward(c, aux.value(), "tanh");
+  else if (act == 4) c = at::gelu_backward(c, aux.value(), "none");
+  else if (act >= 5) {           // fused fwd: keep pre-act in aux
+    aux.value().copy_(c);
+    c = at::gelu(c, "tanh");
+  }
+  return c;
+}
+
 at::Tensor gemm_nt_act(const at::Tensor& a, const at::Tensor& bt,
                        const std::optional<at::Tensor>& bias, int64_t act,
                        const std::optional<at::Tensor>& aux) {
@@ -1353,17 +1665,7 @@ at::Tensor gemm_nt_act(const at::Tensor& a, const at::Tensor& bt,
     hipLaunchKernelGGL(gemm_nt_128, dim3(nwg), dim3(256), lds, stream,
         (const bf16*)a.data_ptr(), (const bf16*)bt.data_ptr(),
         (bf16*)c.data_ptr(), bias_p, (int)M, (int)N, (int)K);
-    if (act) {
-      // edge-shape path: apply the activation as a separate aten pass
-      if (act == 1) c = at::gelu(c, "tanh");
-      else if (act == 3) c = at::gelu(c);
-      else if (act == 2) c = at::gelu_backward(c, aux.value(), "tanh");
-      else if (act == 4) c = at::gelu_backward(c, aux.value(), "none");
-      else if (act >= 5) {           // fused fwd: keep pre-act in aux
-        aux.value().copy_(c);
-        c = at::gelu(c, "tanh");
-      }
-    }
+    c = act_pass(c, act, aux);
   }
   return c;
 }
@@ -1371,6 +1673,63 @@ at::Tensor gemm_nt_act(const at::Tensor& a, const at::Tensor& bt,
 at::Tensor gemm_nt(const at::Tensor& a, const at::Tensor& bt,
                    const std::optional<at::Tensor>& bias) {
   return gemm_nt_act(a, bt, bias, 0, std::nullopt);
+}
+
+// C = a @ b (+bias), activation epilogue: a [M,K] and b [K,N] row-major, the
+// dX backward with the weight as it lies.  No host synchronisation, nothing
+// allocated but the output (and the aten activation's on the edge path).
+at::Tensor gemm_nn_act(const at::Tensor& a, const at::Tensor& b,
+                       const std::optional<at::Tensor>& bias, int64_t act,
+                       const std::optional<at::Tensor>& aux) {
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dtype() == at::kBFloat16 &&
+              b.dtype() == at::kBFloat16, "gemm_nn: bf16 device tensors");
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.is_contiguous() &&
+              b.is_contiguous(), "gemm_nn wants row-major a [M,K], b [K,N]");
+  const long M = a.size(0), K = a.size(1), N = b.size(1);
+  TORCH_CHECK(b.size(0) == K, "gemm_nn: reduce dims must match");
+  TORCH_CHECK(M >= 1 && K >= NN_BK && K % NN_BK == 0 && N >= 8 && N % 8 == 0,
+              "gemm_nn: M >= 1, K % 32 == 0, N % 8 == 0");
+  TORCH_CHECK(M < (1L << 31) && K < (1L << 31) && N < (1L << 31));
+  TORCH_CHECK((uintptr_t)a.data_ptr() % 16 == 0 &&
+              (uintptr_t)b.data_ptr() % 16 == 0,
+              "gemm_nn: a and b must be 16-byte aligned");
+  TORCH_CHECK(act >= 0 && act <= 6, "gemm_nn: activation modes 0 to 6");
+  const bool use_aux = act == 2 || act >= 4;   // 1 and 3 are plain forward
+  TORCH_CHECK(!use_aux || aux, "gemm_nn: activation modes 2/4/5/6 need aux");
+  if (use_aux)
+    TORCH_CHECK(aux->is_cuda() && aux->dtype() == at::kBFloat16 &&
+                aux->is_contiguous() && aux->dim() == 2 &&
+                aux->size(0) == M && aux->size(1) == N &&
+                (uintptr_t)aux->data_ptr() % 16 == 0,
+                "gemm_nn: aux must be a contiguous, aligned bf16 [M,N]");
+  if (bias)
+    TORCH_CHECK(bias->is_cuda() && bias->dtype() == at::kBFloat16 &&
+                bias->is_contiguous() && bias->numel() == N,
+                "gemm_nn: bias must be a contiguous bf16 [N]");
+  auto c = at::empty({M, N}, a.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const bf16* bias_p = bias ? (const bf16*)bias->data_ptr() : nullptr;
+  if (K % BK2 == 0 && M >= BM2 && N >= BN2) {
+    const long nwg = ((M + BM2 - 1) / BM2) * ((N + BN2 - 1) / BN2);
+    TORCH_CHECK(nwg < (1L << 31), "gemm_nn: too many tiles for one launch");
+    bf16* aux_p = use_aux ? (bf16*)aux->data_ptr() : nullptr;
+    hipLaunchKernelGGL(gemm_nn_256, dim3((unsigned)nwg), dim3(512), 2 * BUF_B,
+        stream, (const bf16*)a.data_ptr(), (const bf16*)b.data_ptr(),
+        (bf16*)c.data_ptr(), bias_p, aux_p, (int)act, (int)M, (int)N, (int)K);
+  } else {
+    const long nwg = ((M + NN_BM - 1) / NN_BM) * ((N + 127) / 128);
+    TORCH_CHECK(nwg < (1L << 31), "gemm_nn: too many tiles for one launch");
+    hipLaunchKernelGGL(gemm_nn_128, dim3((unsigned)nwg), dim3(256), 32768,
+        stream, (const bf16*)a.data_ptr(), (const bf16*)b.data_ptr(),
+        (bf16*)c.data_ptr(), bias_p, (int)M, (int)N, (int)K);
+    c = act_pass(c, act, aux);
+  }
+  return c;
+}
+
+at::Tensor gemm_nn(const at::Tensor& a, const at::Tensor& b,
+                   const std::optional<at::Tensor>& bias) {
+  return gemm_nn_act(a, b, bias, 0, std::nullopt);
 }
 
 at::Tensor gelu_fast(const at::Tensor& x) {

@@ -5,9 +5,14 @@ sharded graph's linear-layer matmuls to these ops:
 
 * ``easydist_amd::gemm_nt(a, bt, bias)`` — C = a @ bt.T (+bias), the
   NT shape every traced ``nn.Linear`` forward produces (both operands
-  K-contiguous), and — with a cheap weight-side transpose inserted by the
-  pass — the dX backward too.  CUDA: the 256x256 8-phase MFMA kernel
+  K-contiguous).  CUDA: the 256x256 8-phase MFMA kernel
   (csrc/gemm_kernels.hip), 128x128 for edge shapes.
+* ``easydist_amd::gemm_nn(a, b, bias)`` / ``gemm_nn_act`` — C = a @ b
+  (+bias, activation epilogue) with b [K, N] row-major, the dX backward
+  (dX = dY @ W) on the weight as it lies.  CUDA: the native NN kernels
+  (``gemm_nn_256``, which stages b k-major into transposed-read LDS
+  images, and the 128x128 ``gemm_nn_128`` for edge shapes): no
+  transposed copy of the weight is made.
 * ``easydist_amd::gemm_tn(a, b)`` — C = a.T @ b with BOTH operands
   reduce-dim-strided (the dW backward; transposing the activations
   globally would cost about the GEMM itself).  CUDA: split-R tr-read
@@ -312,11 +317,10 @@ def _nt_gelu_fake(a, bt, bias, tanh_approx):
 
 
 # NN-layout GEMM: C = a @ b with b [K, N] row-major (the dX backward:
-# dX = dY @ W). The HAND kernel wants a K-contiguous B operand, so ITS
-# route pays one weight-sized transpose copy; the hipBLASLt route takes
-# the strided layout natively and skips it. Keeping the transpose INSIDE
-# the op lets the per-shape profiler price each route honestly — the
-# old lowering cloned t(W) in the graph unconditionally.
+# dX = dY @ W). Both routes take that layout as it lies: the hand route is
+# the native NN kernel (ext.gemm_nn, no transposed weight copy), the aten
+# route hipBLASLt's strided mm; the per-shape profiler prices one against
+# the other.
 lib.define("gemm_nn(Tensor a, Tensor b, Tensor? bias) -> Tensor")
 
 
@@ -334,13 +338,11 @@ def _nn_cuda(a, b, bias):
             or not _nt_supported(a, b.t()):   # shape check only (view)
         return _nn_cpu(a, b, bias)
     a = a.contiguous()
+    b_c = bias.contiguous() if bias is not None else None
 
     def hand():
-        # the hand kernel's route INCLUDES its weight transpose copy, so
-        # the profiler prices it honestly against the strided aten mm
-        bt = b.t().contiguous()
-        b_c = bias.contiguous() if bias is not None else None
-        return ext.gemm_nt(a, bt, b_c)
+        # b as it lies ([K, N] row-major): no transposed weight copy
+        return ext.gemm_nn(a, b.contiguous(), b_c)
 
     key = ("nn", a.shape[0], a.shape[1], b.shape[1], bias is not None)
     if _choose(key, hand, lambda: _nn_cpu(a, b, bias)):
@@ -359,7 +361,7 @@ def _nn_fake(a, b, bias):
 
 # gemm_nn with a fused activation epilogue (the dX + gelu_backward
 # fusion when the incoming grad is an NN-layout GEMM): hand route =
-# weight transpose + gemm_nt_act; aten route = strided mm + the
+# the native NN kernel's epilogue; aten route = strided mm + the
 # bandwidth-rate gelu_bwd kernel.
 lib.define("gemm_nn_act(Tensor a, Tensor b, Tensor? bias, int act, "
            "Tensor? aux) -> Tensor")
@@ -377,12 +379,11 @@ def _nn_act_cuda(a, b, bias, act, aux):
             or not _nt_supported(a, b.t()):
         return _nn_act_cpu(a, b, bias, act, aux)
     a = a.contiguous()
+    b_c = bias.contiguous() if bias is not None else None
     x_c = aux.contiguous() if aux is not None else None
 
     def hand():
-        bt = b.t().contiguous()
-        b_c = bias.contiguous() if bias is not None else None
-        return ext.gemm_nt_act(a, bt, b_c, act, x_c)
+        return ext.gemm_nn_act(a, b.contiguous(), b_c, act, x_c)
 
     def aten():
         return _act_fast(ext, _nn_cpu(a, b, bias), act, aux)
